@@ -8,6 +8,13 @@ inflated back, inputs resident in HBM.  One step = deflate of the shard +
 shard.  value = bytes of all shards / (time of the step) in MB/s (1e6 B/s).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--level L]
+                  [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result
+  line.  --dump-outputs DIR also writes what the last timed step left in the
+  caller's buffers as DIR/<name>.npy (dump_outputs below).  --full adds what
+  takes runs or checks of its own: the deflate / inflate split, the round-trip
+  and oracle parity check, the checksum kernel's rate, the PCIe-inclusive
+  host-buffer rates and the CPU baseline.
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N,
   or bench.py --gpus N alone (it launches the N ranks itself).
   Default size per GPU: 1 GiB at N=1 (configs[1]); 8 GiB at N>1, so that N=8
@@ -45,10 +52,15 @@ def parse():
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--corpus", choices=("text", "mixed"), default="text")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL bitstream gather")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline value does not need: the "
+                         "deflate / inflate split, round trip and oracle parity, checksum rate, "
+                         "host-buffer (PCIe) rates, CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the PCIe-inclusive host-API rate (profiling passes: keeps every "
-                         "launch of a kernel at the bench size)")
+                    help="with --full: skip the PCIe-inclusive host-API rates")
     ap.add_argument("--cpu-sample", type=int, default=256 << 20)
     ap.add_argument("--stream-sample", type=int, default=256 << 20,
                     help="bytes for the drop-in inflator's 32 KiB-read rate")
@@ -523,6 +535,54 @@ def sq_compute(kt, steps, level, size, corpus="text", min_ms=1.0):
     return None
 
 
+DUMP_BLOCKS = 32          # blocks whose bytes --dump-outputs keeps
+
+
+def dump_outputs(J, path, tag, nb, d_out, d_csz, d_coff, d_tot, d_back, d_us, d_err):
+    """--dump-outputs: what a caller of deflate_device + inflate_device holds
+    after the last timed step, as float64 / float32 .npy files under `path`:
+      comp_sizes, comp_offsets, comp_total     the deflate's size index, whole
+      inflated_sizes, inflate_errors           the inflate's per-block results, whole
+      sample_blocks                            a fixed, seeded choice of <= 32 blocks
+                                               (always the first and the last)
+      comp_sample[i, :comp_sizes[b]]           the compressed bytes of block b =
+                                               sample_blocks[i], zero-padded to bound(64 KiB)
+      inflated_sample[i, :]                    the 64 KiB that block b inflated to
+    About 25 MB at any size.  The corpus is seeded, so the same arguments give
+    the same inputs and two builds can be compared file for file.  `tag` is
+    ".rankR" on a multi-GPU run (each rank dumps its own shard)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    csz = d_csz.cpu().numpy().astype(np.int64)
+    coff = d_coff.cpu().numpy().astype(np.int64)
+    pick = np.zeros(0, dtype=np.int64)
+    if nb:
+        rng = np.random.default_rng(0x6A64)
+        more = rng.choice(nb, size=min(nb, DUMP_BLOCKS - 2), replace=False)
+        pick = np.unique(np.concatenate([[0, nb - 1], more])).astype(np.int64)
+    slot = J.bound(BS)
+    comp = np.zeros((pick.size, slot), dtype=np.float32)
+    back = np.zeros((pick.size, BS), dtype=np.float32)
+    for i, b in enumerate(pick):
+        a = min(max(int(coff[b]), 0), d_out.numel())
+        c = min(max(int(csz[b]), 0), slot)
+        got = d_out[a:a + c].cpu().numpy()
+        comp[i, :got.size] = got
+        back[i] = d_back[b * BS:(b + 1) * BS].cpu().numpy()
+    arrays = {
+        "comp_sizes": csz.astype(np.float64),
+        "comp_offsets": coff.astype(np.float64),
+        "comp_total": d_tot.cpu().numpy().astype(np.float64),
+        "inflated_sizes": d_us.cpu().numpy().astype(np.float64),
+        "inflate_errors": d_err.cpu().numpy().astype(np.float64),
+        "sample_blocks": pick.astype(np.float64),
+        "comp_sample": comp,
+        "inflated_sample": back,
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
 def workload_name(args, n, nb, world):
     what = ("Zipf text" if args.corpus == "text" else "Silesia-like mixed-entropy")
     tag = ("C4" if world > 1 and args.corpus == "text" else
@@ -621,18 +681,20 @@ def main():
         step()
     torch.cuda.synchronize()
 
-    # deflate / inflate split, measured on the same stream (outside the timed loop)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    ev[0].record(stream)
-    J.deflate_device(d_in.data_ptr(), n, d_out.data_ptr(), cap, d_csz.data_ptr(),
-                     d_coff.data_ptr(), d_tot.data_ptr(), level=args.level,
-                     lastflush=lastflush, stream=sp)
-    ev[1].record(stream)
-    J.inflate_device(d_out.data_ptr(), cap, d_coff.data_ptr(), d_csz.data_ptr(), nb,
-                     d_back.data_ptr(), d_us.data_ptr(), d_err.data_ptr(), stream=sp)
-    ev[2].record(stream)
-    torch.cuda.synchronize()
-    t_def, t_inf = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    t_def = t_inf = None
+    if args.full:
+        # deflate / inflate split, measured on the same stream (outside the timed loop)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(stream)
+        J.deflate_device(d_in.data_ptr(), n, d_out.data_ptr(), cap, d_csz.data_ptr(),
+                         d_coff.data_ptr(), d_tot.data_ptr(), level=args.level,
+                         lastflush=lastflush, stream=sp)
+        ev[1].record(stream)
+        J.inflate_device(d_out.data_ptr(), cap, d_coff.data_ptr(), d_csz.data_ptr(), nb,
+                         d_back.data_ptr(), d_us.data_ptr(), d_err.data_ptr(), stream=sp)
+        ev[2].record(stream)
+        torch.cuda.synchronize()
+        t_def, t_inf = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
 
     # timed region: K steps, per-kernel HIP events on the engine's stream
     J.prof_enable(True)
@@ -653,10 +715,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
-    # correctness of the last step (outside the timed region)
-    ok = bool(torch.equal(d_back, d_in)) and int(d_err.abs().sum().item()) == 0
+    if args.dump_outputs:
+        dump_outputs(J, args.dump_outputs, f".rank{rank}" if world > 1 else "", nb,
+                     d_out, d_csz, d_coff, d_tot, d_back, d_us, d_err)
+
+    # --full: correctness of the last step (outside the timed region)
+    ok = True
+    if args.full:
+        ok = bool(torch.equal(d_back, d_in)) and int(d_err.abs().sum().item()) == 0
     ctotal = int(d_tot.item())
-    if rank == 0:
+    if args.full and rank == 0:
         from oracle import jdoracle as O
         csz = d_csz.cpu().numpy().astype(np.int64)
         coff = d_coff.cpu().numpy()
@@ -666,9 +734,10 @@ def main():
                             flush=lastflush if b == nb - 1 else 2)
             ok &= gpu_blk == ref
     if world > 1:
-        f = torch.tensor([1 if ok else 0], device=dev)
-        dist.all_reduce(f, op=dist.ReduceOp.MIN)
-        ok = bool(f.item())
+        if args.full:
+            f = torch.tensor([1 if ok else 0], device=dev)
+            dist.all_reduce(f, op=dist.ReduceOp.MIN)
+            ok = bool(f.item())
         tot = torch.tensor([ctotal], dtype=torch.int64, device=dev)
         dist.all_reduce(tot)
         call = int(tot.item())
@@ -709,15 +778,6 @@ def main():
                 "bytes_per_gpu": n,
                 "parallelism": f"shard{world}" + ("+rccl_gather" if gather else ""),
                 "ratio": round(call / total_bytes, 6),
-                "deflate_MBps_per_gpu": round(n / (t_def / 1e3) / 1e6, 2),
-                "inflate_MBps_per_gpu": round(n / (t_inf / 1e3) / 1e6, 2),
-                # SURVEY.md §8d per direction: (N + C) / t, and the north
-                # star's HBM-read fraction (N / t_def, C / t_inf over 8 TB/s)
-                "deflate_NplusC_GBps": round((n + ctotal) / (t_def / 1e3) / 1e9, 2),
-                "inflate_NplusC_GBps": round((n + ctotal) / (t_inf / 1e3) / 1e9, 2),
-                "deflate_hbm_read_frac": round(n / (t_def / 1e3) / 1e9 / HBM_PEAK_GBPS, 5),
-                "inflate_hbm_read_frac": round(ctotal / (t_inf / 1e3) / 1e9 / HBM_PEAK_GBPS, 5),
-                "roundtrip_ok": ok,
                 "kernel_ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in kt.items()},
             },
             "roofline": {
@@ -740,9 +800,21 @@ def main():
             },
             "cpu_baseline": None,
         }
-        if world == 1:
+        if args.full:
+            line["config"].update({
+                "deflate_MBps_per_gpu": round(n / (t_def / 1e3) / 1e6, 2),
+                "inflate_MBps_per_gpu": round(n / (t_inf / 1e3) / 1e6, 2),
+                # SURVEY.md §8d per direction: (N + C) / t, and the north
+                # star's HBM-read fraction (N / t_def, C / t_inf over 8 TB/s)
+                "deflate_NplusC_GBps": round((n + ctotal) / (t_def / 1e3) / 1e9, 2),
+                "inflate_NplusC_GBps": round((n + ctotal) / (t_inf / 1e3) / 1e9, 2),
+                "deflate_hbm_read_frac": round(n / (t_def / 1e3) / 1e9 / HBM_PEAK_GBPS, 5),
+                "inflate_hbm_read_frac": round(ctotal / (t_inf / 1e3) / 1e9 / HBM_PEAK_GBPS, 5),
+                "roundtrip_ok": ok,
+            })
+        if args.full and world == 1:
             line["config"]["checksum"] = checksum_rate(J, d_in, n, host, sp)
-        if world == 1 and not args.no_host_api:
+        if args.full and world == 1 and not args.no_host_api:
             line["config"]["host_api_pcie"] = host_api_rate(J, host, args.level, 256 << 20)
             line["config"]["dropin_pcie"] = dropin_rate(J, host, args.level, 256 << 20)
             line["config"]["dropin_stream_pcie"] = dropin_stream_rate(J, host, args.level,
@@ -751,7 +823,7 @@ def main():
                 J, host, args.level, args.stream_sample // 8, threads=8)
             line["config"]["zstrm_gzip_pcie"] = zstrm_rate(J, host, args.level, 256 << 20)
             line["config"]["foreign_stream_pcie"] = foreign_stream_rate(J, host, args.foreign_sample)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(host, args.level, args.cpu_sample)
         print(json.dumps(line), flush=True)
     if world > 1:

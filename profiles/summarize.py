@@ -51,7 +51,7 @@ def main(out, tag, name="pmc_summary.json", extra=""):
     summary = {
         "tag": tag,
         "command": ("rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --steps 1 --warmup 0 "
-                    "--no-cpu --no-host-api " + extra).strip(),
+                    "--full --no-cpu --no-host-api " + extra).strip(),
         "correction": "FETCH_SIZE x2 (gfx950), KiB -> bytes; averages over dispatches",
         "workload": {"level": cfg.get("level"), "bytes": cfg.get("bytes_per_gpu"),
                      "workload": cfg.get("workload")},

@@ -6,8 +6,8 @@
 #   pytest            the whole -m gpu suite
 #   pytest:EXPR       -m gpu -k EXPR
 #   smoke             __graft_entry__.smoke()
-#   bench             python bench.py (the driver's default line)
-#   quick             python bench.py --steps 5 --warmup 1 --no-cpu --no-host-api
+#   bench             python bench.py --full (every section of the result line)
+#   quick             python bench.py --steps 5 --warmup 1 --full --no-cpu --no-host-api
 #   probe             tools/probe.py (per-kernel ms, output CRC)
 #   probe:VAR=VAL     the same with an environment switch (e.g. JD_CHAINS_SERIAL=1)
 #   var:NAME          tools/probe.py on the variant library tools/var/NAME
@@ -52,8 +52,8 @@ for s in "$@"; do
         pytest:*) step "pytest_${s#pytest:}" 900 python -u -m pytest tests -m gpu -x -v --timeout 200 \
                        --timeout-method thread -k "${s#pytest:}" ;;
         smoke) step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) step bench 600 python bench.py ;;
-        quick) step quick 300 python bench.py --steps 5 --warmup 1 --no-cpu --no-host-api ;;
+        bench) step bench 600 python bench.py --full ;;
+        quick) step quick 300 python bench.py --steps 5 --warmup 1 --full --no-cpu --no-host-api ;;
         probe) step probe 300 python tools/probe.py ;;
         probe:*) env "${s#probe:}" timeout -k 10 300 python tools/probe.py > "$OUT/probe_${s#probe:}.log" 2>&1 \
                      || { echo "probe ${s#probe:} failed"; tail -5 "$OUT/probe_${s#probe:}.log"; exit 1; }
@@ -86,7 +86,7 @@ for s in "$@"; do
                      python tools/stream_rate.py ;;
         sq:*) SIZE=$((1<<30)) SQTAG=${s#sq:} step "sq_${s#sq:}" 900 bash tools/prof_counters.sh "_${s#sq:}" ;;
         c5) step c5 600 python bench.py --corpus mixed --level 9 --size 4294967296 --steps 3 --warmup 1 \
-                --no-cpu --no-host-api ;;
+                --full --no-cpu --no-host-api ;;
         *) echo "unknown step $s"; exit 2 ;;
     esac
 done
