@@ -767,6 +767,13 @@ __device__ static inline uint32_t lds_word(const uint32_t* w32, uint32_t i)
     return __builtin_amdgcn_alignbyte(c, a, i);     /* uses i[1:0] only */
 }
 
+/* 8 window bytes from byte offset i, from three aligned reads */
+__device__ static inline uint64_t lds_word2(const uint32_t* w32, uint32_t i)
+{
+    const uint32_t a = w32[i >> 2], b = w32[(i >> 2) + 1], c = w32[(i >> 2) + 2];
+    return ((uint64_t) __builtin_amdgcn_alignbyte(c, b, i) << 32) | __builtin_amdgcn_alignbyte(b, a, i);
+}
+
 __device__ static inline uint64_t lds_dword2(const uint32_t* w32, uint32_t i)
 {
     uint64_t v;
@@ -923,10 +930,15 @@ __global__ __launch_bounds__(1024) void k_match(const uint8_t* __restrict__ in,
      * p side (pw at offset pt, mask pm) changes only with cl */
     uint32_t cl = 2, co = 0, l24 = 0, o24 = 0, left = chain, pw = 0, pt = 0, pm = 0xffffffu;
     bool have24 = false;
+    /* the 8 window bytes at p, read once when the position is taken: the
+     * first matchlen step of every candidate reads only the candidate side,
+     * and the cl = 2 reject word is their low 3 bytes */
+    uint64_t p8 = 0;
     if (live) {
         q = (int32_t) (p - lo) - (int32_t) pv[p - lo];
         qmin = max((int32_t) (p - lo) - (int32_t) (JD_WSIZE - 1), 0);
-        pw = lds_word(w32, p - lo) & pm;
+        p8 = lds_word2(w32, p - lo);
+        pw = (uint32_t) p8 & pm;
     }
 
     while (live) {
@@ -958,24 +970,23 @@ __global__ __launch_bounds__(1024) void k_match(const uint8_t* __restrict__ in,
                 uint32_t m = 0;
                 const uint32_t ip = p - lo, iq = (uint32_t) q;
                 if (ML16) {
-                while (m < JD_MAXMATCH) {
                     uint4 xa, xb;
-                    __builtin_memcpy(&xa, (const uint8_t*) w32 + ip + m, 16);
-                    __builtin_memcpy(&xb, (const uint8_t*) w32 + iq + m, 16);
-                    const uint64_t x0 = ((uint64_t) (xa.y ^ xb.y) << 32) | (xa.x ^ xb.x);
-                    const uint64_t x1 = ((uint64_t) (xa.w ^ xb.w) << 32) | (xa.z ^ xb.z);
-                    if (x0 | x1) {
-                        m += x0 ? __builtin_ctzll(x0) >> 3 : 8 + (__builtin_ctzll(x1) >> 3);
-                        break;
+                    __builtin_memcpy(&xb, (const uint8_t*) w32 + iq, 16);
+                    const uint64_t a1 = lds_dword2(w32, ip + 8);
+                    uint64_t x0 = p8 ^ (((uint64_t) xb.y << 32) | xb.x);
+                    uint64_t x1 = a1 ^ (((uint64_t) xb.w << 32) | xb.z);
+                    while (!(x0 | x1) && (m += 16) < JD_MAXMATCH) {
+                        __builtin_memcpy(&xa, (const uint8_t*) w32 + ip + m, 16);
+                        __builtin_memcpy(&xb, (const uint8_t*) w32 + iq + m, 16);
+                        x0 = ((uint64_t) (xa.y ^ xb.y) << 32) | (xa.x ^ xb.x);
+                        x1 = ((uint64_t) (xa.w ^ xb.w) << 32) | (xa.z ^ xb.z);
                     }
-                    m += 16;
-                }
+                    if (x0 | x1) m += x0 ? __builtin_ctzll(x0) >> 3 : 8 + (__builtin_ctzll(x1) >> 3);
                 } else {
-                while (m < JD_MAXMATCH) {
-                    const uint64_t x = lds_dword2(w32, ip + m) ^ lds_dword2(w32, iq + m);
-                    if (x) { m += __builtin_ctzll(x) >> 3; break; }
-                    m += 8;
-                }
+                    uint64_t x = p8 ^ lds_dword2(w32, iq);
+                    while (!x && (m += 8) < JD_MAXMATCH)
+                        x = lds_dword2(w32, ip + m) ^ lds_dword2(w32, iq + m);
+                    if (x) m += __builtin_ctzll(x) >> 3;
                 }
                 m = min(m, JD_MAXMATCH);
                 if (m > cl) {
@@ -1013,7 +1024,8 @@ __global__ __launch_bounds__(1024) void k_match(const uint8_t* __restrict__ in,
                 qmin = max((int32_t) (p - lo) - (int32_t) (JD_WSIZE - 1), 0);
                 pt = 0;
                 pm = 0xffffffu;
-                pw = lds_word(w32, p - lo) & pm;
+                p8 = lds_word2(w32, p - lo);
+                pw = (uint32_t) p8 & pm;
             }
         }
     }
