@@ -12,8 +12,12 @@
  *   k_chains<3>  hash-3 chain links for every position   (shlist/schain)
  *   k_match      chain walk for every position, both chain budgets and the
  *                3-byte candidate, all in LDS                (getmatch2)
- *   k_parse      the lazy / greedy parse + block-split heuristic, one lane
- *                per block, reading the match records      (compress2/1)
+ *   k_parse      levels 1-5: the greedy parse, one lane per block reading
+ *                the match records                          (compress1)
+ *   k_pweight / k_porder / k_pspec / k_psync / k_pjoin
+ *                levels 6-9: the lazy parse, walked speculatively per
+ *                quarter block and joined by one wave per block, which
+ *                also runs the block-split heuristic        (compress2)
  *   k_emit       per deflate block: histogram, Huffman build, trees, and
  *                bit packing by a workgroup prefix scan     (flushblock)
  *   k_scan / k_compact  concatenate the per-block bitstreams
@@ -1406,21 +1410,19 @@ __global__ __launch_bounds__(NT, K2S_W) void k_match_sl(const uint8_t* __restric
 
 
 /* ------------------------------------------------------------------------ */
-/* K3: the parser.  One lane per block; the lane runs compress2 :2826-2949
- * (levels 6-9) or compress1 :2472-2505 (levels 1-5) over the match records,
- * writes one uint32 token per literal/match and closes a deflate block on
- * the token-list-full rule (:2910) and the split heuristic (:2927-2948).
+/* K3, levels 1-5: the greedy parser.  One lane per block runs compress1
+ * :2472-2505 over the match records (read from global memory), writes one
+ * uint32 token per literal/match and closes a deflate block on the
+ * token-list-full rule (:2910).  Levels 6-9 take the split parse below.
  * ------------------------------------------------------------------------ */
 struct ParseArgs {
     const uint64_t* rec;
-    const uint16_t* prev4;
     const uint8_t* in;
     uint64_t n;
     uint32_t bs, nblocks;
     uint32_t* tokens;
     uint32_t* dbinfo;      /* per block: [ndb, (tokend, slots) x JD_MAXDB] */
-    uint32_t good, lzcap, nice, half;
-    int lazy;
+    uint32_t lzcap;
 };
 
 /* byte of the block, zero past its end (the zeroed window, deflator.c:499) */
@@ -1546,283 +1548,66 @@ __device__ static inline uint32_t lsym_bf(uint32_t len)
 
 #define DBSTRIDE (1 + 2 * JD_MAXDB)
 
-/* Per-lane LDS ring of the block's match records and bytes.  Each step
- * reads the record of the next position and of the jump target; from global
- * memory the step waits for the slowest of 64 lanes' gathers every time.
- * The ring is filled in 16-position chunks, two per batch, issued PR_K steps
- * before they are written to LDS, so the load latency overlaps the steps;
- * a position past the ring (a long jump) is read from global memory in a
- * rare wave-uniform branch. */
-#define PR_W    256u                    /* positions per lane ring           */
-#define PR_C    16u                     /* positions per chunk               */
-#define PR_K    4u                      /* steps between batches             */
-#define PR_RS   (PR_W * 8u + 16u)       /* rec ring row bytes (padded)       */
-#define PR_SS   (PR_W + 16u)            /* byte ring row bytes (padded)      */
-#define PR_VMCNT0 0x0f70                /* s_waitcnt vmcnt(0), gfx9 encoding  */
-
-typedef uint32_t pr_v4 __attribute__((ext_vector_type(4)));
-struct PrStage { pr_v4 a, b, c, d, e, f, g, h, s; };
-
-struct ParseShared {
-    uint8_t rr[64 * PR_RS];
-    uint8_t sr[64 * PR_SS];
-    uint32_t hist[32 * 64];             /* curr | prv << 16 per bucket       */
-};
-
 __global__ __launch_bounds__(64) void k_parse(ParseArgs a)
 {
-    __shared__ ParseShared sh;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t b = blockIdx.x * 64 + lane;
-    const bool on = b < a.nblocks;
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.nblocks) return;
 
-    const uint32_t len = on ? blk_len(a.n, a.bs, b) : 0;
-    const uint64_t base = (uint64_t) (on ? b : 0) * a.bs;
+    const uint32_t len = blk_len(a.n, a.bs, b);
+    const uint64_t base = (uint64_t) b * a.bs;
     const uint64_t* rec = a.rec + base;
-    const uint16_t* prev4 = a.prev4 + base;
     const uint8_t* src = a.in + base;
-    const uint8_t* bufend = a.in + a.n;
     uint32_t* tok = a.tokens + base;
-    uint32_t* dbi = a.dbinfo + (uint64_t) (on ? b : 0) * DBSTRIDE;
-    uint8_t* rr = sh.rr + lane * PR_RS;
-    uint8_t* sr = sh.sr + lane * PR_SS;
-    uint32_t* hist = sh.hist;
-
-    for (int j = 0; j < 32; j++) hist[j * 64 + lane] = 0;
-    uint32_t obscount = 0, newcount = 0, obstotal = 0;
+    uint32_t* dbi = a.dbinfo + (uint64_t) b * DBSTRIDE;
     uint32_t cur = 0, nt = 0, slots = 0, ndb = 0;
-    uint32_t hm = 0, hl = 0, ho = 0, ds = 0, lastc = 0;
 
-#define RESETOBS() do { for (int j_ = 0; j_ < 32; j_++) hist[j_ * 64 + lane] = 0; obscount = newcount = obstotal = 0; } while (0)
 #define CLOSEDB() do { if (ndb < JD_MAXDB) { dbi[1 + 2 * ndb] = nt; dbi[2 + 2 * ndb] = slots; } ndb++; slots = 0; } while (0)
 
-    if (a.lazy) {
-        /* ring: positions [.., rdy) are in LDS (those >= cur valid); np
-         * chunks in flight in st0/st1 for [rdy, rdy + 16 np) */
-        uint32_t rdy = 0, np = 0;
-        PrStage st0, st1;
-#define PR_LD(st_, q_)                                                                 \
-        do {                                                                           \
-            const pr_v4* g_ = (const pr_v4*) (rec + (q_));                             \
-            st_.a = g_[0]; st_.b = g_[1]; st_.c = g_[2]; st_.d = g_[3];                \
-            st_.e = g_[4]; st_.f = g_[5]; st_.g = g_[6]; st_.h = g_[7];                \
-            st_.s = *(const pr_v4*) (src + (q_));                                      \
-        } while (0)
-#define PR_ST(st_, q_)                                                                 \
-        do {                                                                           \
-            const uint32_t w_ = (q_) & (PR_W - 1);                                     \
-            pr_v4* d_ = (pr_v4*) (rr + w_ * 8);                                        \
-            d_[0] = st_.a; d_[1] = st_.b; d_[2] = st_.c; d_[3] = st_.d;                \
-            d_[4] = st_.e; d_[5] = st_.f; d_[6] = st_.g; d_[7] = st_.h;                \
-            *(pr_v4*) (sr + w_) = st_.s;                                               \
-        } while (0)
-#define PR_ISSUE()                                                                     \
-        do {                                                                           \
-            np = 0;                                                                    \
-            if (rdy + PR_C <= len && rdy + PR_C <= cur + PR_W) {                       \
-                PR_LD(st0, rdy);                                                       \
-                np = 1;                                                                \
-                if (rdy + 2 * PR_C <= len && rdy + 2 * PR_C <= cur + PR_W) {           \
-                    PR_LD(st1, rdy + PR_C);                                            \
-                    np = 2;                                                            \
-                }                                                                      \
-            }                                                                          \
-        } while (0)
-#define PR_LAND()                                                                      \
-        do {                                                                           \
-            if (np >= 1) PR_ST(st0, rdy);                                              \
-            if (np >= 2) PR_ST(st1, rdy + PR_C);                                       \
-            rdy += np * PR_C;                                                          \
-            if (rdy < (cur & ~(PR_C - 1))) rdy = cur & ~(PR_C - 1);                    \
-        } while (0)
-#define PR_RING(p_, r_, c_)                                                            \
-        do {                                                                           \
-            const uint32_t q_ = (p_) & (PR_W - 1);                                     \
-            r_ = *(const uint64_t*) (rr + q_ * 8);                                     \
-            c_ = sr[q_];                                                               \
-        } while (0)
-#define PR_MISS(p_, r_, c_)                                                            \
-        do {                                                                           \
-            if ((p_) >= rdy) {                                                         \
-                r_ = rec[p_];                                                          \
-                c_ = src[p_];                                                          \
-            }                                                                          \
-        } while (0)
-        /* prime half the ring synchronously */
-        for (uint32_t k = 0; k < PR_W / 2 / (2 * PR_C); k++) {
-            PR_ISSUE();
-            PR_LAND();
+    /* a match needs length > 3 */
+    while (cur < len) {
+        const uint64_t r = rec[cur];
+        const uint32_t l = min((uint32_t) r & 511, len - cur), o = (uint32_t) (r >> 9) & 0x7fff;
+        if (l > 3) {
+            tok[nt++] = jd_tok_match(l, o);
+            slots += 3;
+            cur += l - 1;
+        } else {
+            tok[nt++] = src[cur];
+            slots += 1;
         }
-        PR_ISSUE();
-        uint32_t step = 0;
-        uint64_t r = 0;
-        uint32_t c = 0;
-        if (len) {
-            PR_RING(0u, r, c);
-            PR_MISS(0u, r, c);
-        }
-
-        /* The next position is always cur + 1 or a target known from the
-         * record before the step is decided (cur + l48 when a match reaches
-         * `good`, cur + hl - 1 when the held match is emitted), so both
-         * candidates' record and byte are read at the top of the step. */
-        while (__ballot(cur < len)) {
-            if (++step == PR_K) {
-                step = 0;
-                PR_LAND();
-                PR_ISSUE();
-            }
-            if (cur < len) {
-                /* records hold raw lengths; truncate to the block end here */
-                const uint32_t rem = len - cur;
-                const uint32_t raw48 = (uint32_t) r & 511;
-                const uint32_t l48 = min(raw48, rem), o48 = (uint32_t) (r >> 9) & 0x7fff;
-                const uint32_t n1 = cur + 1;
-                /* selects, not branches (__builtin_unpredictable and the
-                 * masks keep LLVM from turning them into divergent code) */
-                const uint32_t nf = __builtin_unpredictable(l48 >= a.good) ? cur + l48 : n1;
-                const uint32_t n2 = nf + ((cur + hl - 1 - nf) & (0u - hm));      /* hm ? .. : nf */
-                /* a candidate at or past the block end is never stepped on */
-                const uint32_t n1c = min(n1, len - 1), n2c = min(n2, len - 1);
-                uint64_t r1, r2;
-                uint32_t c1, c2;
-                PR_RING(n1c, r1, c1);
-                PR_RING(n2c, r2, c2);
-                if (__ballot(n2c >= rdy)) {            /* n1c <= n2c */
-                    PR_MISS(n1c, r1, c1);
-                    PR_MISS(n2c, r2, c2);
-                    /* wait here: a miss load left in flight would make every
-                     * later ring read wait for the batch in flight */
-                    __builtin_amdgcn_s_waitcnt(PR_VMCNT0);
-                }
-                /* one step of compress2 :2826-2906: the fresh step
-                 * (getmatch2(2, shrt), far-3 rule, good) and the held step
-                 * (getmatch2(prev-1, 0), accept rule) are both evaluated and
-                 * one of their outcomes is kept */
-                const bool H = hm != 0;
-                const uint32_t s3 = (uint32_t) (r >> 48);
-                const bool use3 = raw48 < 3 && ds && s3 && rem >= 3;
-                uint32_t fml = use3 ? 3 : l48;
-                const uint32_t fmo = use3 ? s3 : o48;
-                fml = (fml == 3 && fmo > 8192) ? 2 : fml;
-                const uint32_t l24 = min((uint32_t) (r >> 24) & 511, rem), o24 = (uint32_t) (r >> 33) & 0x7fff;
-                uint32_t hml = hl >= 4 ? l24 : l48, hmo = hl >= 4 ? o24 : o48;
-                if (__ballot(H && hl - 1 >= a.nice)) {
-                    if (H && hl - 1 >= a.nice) held_long(src, len, bufend, prev4, cur, hl - 1, a.half, &hml, &hmo);
-                }
-                const int dl = (int) hml - (int) hl;
-                const bool acc = __builtin_unpredictable(
-                    H & (hml >= hl) & ((dl > 4) | ((dl * 4 + jd_ilog2(ho | 1) - jd_ilog2(hmo | 1)) >= 2)));
-                const bool fm = !H & (fml >= 3);
-                const bool emit_fresh = fm & (fml >= a.good);
-                const bool hold = fm & (fml < a.good);
-                const bool emit_held = H & !acc;
-                const bool emit_match = __builtin_unpredictable(emit_fresh | emit_held);
-                const bool emit_lit = (!H & (fml < 3)) | acc;
-                const uint32_t mlen = H ? hl : fml, moff = H ? ho : fmo;
-                const uint32_t lit = H ? lastc : c;
-                /* emission without a branch: the token is stored at tok[nt]
-                 * on every step and kept only when nt advances (a step that
-                 * emits nothing is a hold, so nt < cur < len there) */
-                const uint32_t em = (emit_match || emit_lit) ? 1u : 0u;
-                tok[nt] = emit_match ? jd_tok_match(mlen, moff) : lit;
-                nt += em;
-                slots += emit_match ? 3u : em;
-                const uint32_t mb = 16 + (lsym_bf(mlen) >> 1), lb = lit >> 4;
-                const uint32_t bk = lb ^ ((mb ^ lb) & (0u - (uint32_t) emit_match));
-                atomicAdd(&hist[bk * 64 + lane], em);
-                newcount += em;
-                obstotal += emit_match ? mlen : em;
-                const uint32_t adv = emit_fresh ? fml : emit_held ? hl - 1 : 1;
-                hm = (hold || acc) ? 1 : 0;
-                hl = hold ? fml : acc ? hml : hl;
-                ho = hold ? fmo : acc ? hmo : ho;
-                cur += adv;
-                lastc = c;
-                r = cur == n1 ? r1 : r2;
-                c = cur == n1 ? c1 : c2;
-            }
-            if (!__ballot(slots + 4 > a.lzcap || (newcount >= 512 && obstotal >= 4096))) continue;
-            if (slots + 4 > a.lzcap) {
-                CLOSEDB();
-                RESETOBS();
-            } else if (newcount >= 512 && obstotal >= 4096) {
-                ds = (hist[0 * 64 + lane] & 0xffff) >= 16;
-                /* shouldsplit :2557-2596 */
-                bool split = false;
-                if (obscount > 0) {
-                    uint32_t delta = 0;
-                    for (int j = 0; j < 32; j++) {
-                        const uint32_t h = hist[j * 64 + lane];
-                        const uint32_t x = h >> 16, y = h & 0xffff;
-                        delta += x > y ? x - y : y - x;
-                    }
-                    split = delta >= 320 && obstotal >= 7168;
-                }
-                if (split) {
-                    RESETOBS();
-                    CLOSEDB();
-                } else {
-                    for (int j = 0; j < 32; j++) {
-                        const uint32_t h = hist[j * 64 + lane];
-                        hist[j * 64 + lane] = (((h >> 16) >> 1) + ((h & 0xffff) >> 1)) << 16;
-                    }
-                    obscount += newcount;
-                    newcount = 0;
-                }
-            }
-        }
-#undef PR_LD
-#undef PR_ST
-#undef PR_ISSUE
-#undef PR_LAND
-#undef PR_RING
-#undef PR_MISS
-        if (!on) return;
-    } else {
-        if (!on) return;
-        /* greedy parser, compress1 :2472-2505: a match needs length > 3 */
-        while (cur < len) {
-            const uint64_t r = rec[cur];
-            const uint32_t l = min((uint32_t) r & 511, len - cur), o = (uint32_t) (r >> 9) & 0x7fff;
-            if (l > 3) {
-                tok[nt++] = jd_tok_match(l, o);
-                slots += 3;
-                cur += l - 1;
-            } else {
-                tok[nt++] = src[cur];
-                slots += 1;
-            }
-            cur++;
-            if (slots + 4 > a.lzcap) CLOSEDB();
-        }
+        cur++;
+        if (slots + 4 > a.lzcap) CLOSEDB();
     }
     if (slots) CLOSEDB();
     dbi[0] = ndb;
-#undef RESETOBS
 #undef CLOSEDB
 }
 
 /* ------------------------------------------------------------------------ */
-/* K3, split form (levels 6-9).  The serial lazy parse above is a chain of
- * ~30k dependent steps per block: one lane per block leaves 3 of 4 SIMDs
- * idle and every step waits on its own instruction latency.  Here:
- *   k_pspec   one lane per (block, segment): the lazy step walked from the
- *             segment start with nothing held and doshort = 0, past the
- *             segment end by a margin; every token goes to the segment's
- *             list with its start and whether the walk held nothing there.
- *             A lazy parse re-converges: two walks that reach the same
- *             position with nothing held continue identically.
+/* K3, split form (levels 6-9, and every level of a single-window stream).
+ * The lazy parse, compress2 :2826-2949, is a chain of ~30k dependent steps
+ * per 64 KiB block; walked by one lane per block it leaves 3 of 4 SIMDs idle
+ * and every step waits on its own instruction latency.  So it is cut up:
+ *   k_pweight, k_porder  (block mode) the order in which k_pspec takes the
+ *             blocks, so that similar walks share a wave.
+ *   k_pspec   one lane per (doshort value, block, segment): the lazy step
+ *             (ps_decide) walked from the segment start with nothing held,
+ *             past the segment end by a margin; every token goes to the
+ *             lane's list with its start and whether the walk held nothing
+ *             there.  A lazy parse re-converges: two walks that reach the
+ *             same position with nothing held continue identically.
  *   k_psync   one lane per segment boundary: the first token start past the
  *             boundary at which both neighbouring walks held nothing.
- *   k_pfinal  one lane per block: the exact parse.  It reads tokens from
- *             the lists (following sync points) and runs the block-split
- *             observer (:2910-2948) on them; where the lists cannot be used
- *             -- doshort became 1 (it changes which 3-byte matches count,
- *             :2826-2831), or a list ended without meeting the next -- it
- *             runs the lazy step itself until it stands with nothing held,
- *             doshort 0, at a position some list holds.
- * The token stream and block boundaries are those of k_parse.
+ *   k_pjoin   one wave per block: the exact parse.  It reads tokens from the
+ *             lists (following sync points) and runs the token-list-full
+ *             rule (:2910) and the block-split observer (:2927-2948) on
+ *             them; where the lists cannot be used -- doshort changed (it
+ *             decides which 3-byte matches count, :2826-2831), or a list
+ *             ended without meeting the next -- it runs the lazy step itself
+ *             until it stands with nothing held at an entry of a list.
+ * The result is compress2's own: one uint32 token per literal/match in
+ * tokens, and per block [ndb, (token end, slots) per deflate block] in dbinfo
+ * (tests/test_gpu.py test_split_parse_equals_oracle).
  * ------------------------------------------------------------------------ */
 struct PCtx {
     const uint64_t* rec;
@@ -1877,9 +1662,12 @@ __device__ static inline void ps_targets(const PCtx& x, const PSt& s, uint32_t& 
     n2 = s.hm ? s.cur + s.hl - 1 : nf;
 }
 
-/* one step of compress2 :2826-2906 (the same selects as k_parse), given the
- * records and bytes at both targets; returns whether a token was emitted,
- * its list entry in ex/ey */
+/* The lazy step, compress2 :2826-2906, given the records and bytes at both
+ * targets.  The fresh step (getmatch2(2, shrt), the far 3-byte rule, `good`)
+ * and the held step (getmatch2(held - 1, 0), the accept rule) are both
+ * evaluated and one outcome is kept: selects, so that the lanes of a wave
+ * stay together.  Records hold raw lengths; they truncate at tlen here.
+ * Returns whether a token was emitted, its list entry in ex/ey. */
 template <bool ST>
 __device__ static inline bool ps_decide(const PCtx& x, PSt& s, uint32_t ds, uint32_t n1,
                                         uint64_t r1, uint32_t c1, uint64_t r2, uint32_t c2,
@@ -2023,19 +1811,30 @@ __device__ static inline PCtx ps_ctx(const PSplitArgs& a, uint32_t b, uint32_t l
     return x;
 }
 
-/* k_pspec: per-lane LDS ring of the segment's records and bytes (as in
- * k_parse, smaller: four waves share a CU), filled 16 positions per chunk,
- * two chunks issued every SP_K steps; a target past the ring is read from
- * global memory in a wave-uniform branch */
+/* k_pspec's ring.  Each step of a walk reads the record and byte of the next
+ * position and of the jump target; read from global memory, the step would
+ * wait for the slowest of the wave's 64 gathers every time.  So each lane
+ * keeps the SP_W positions ahead of its walk in an LDS ring of its own
+ * (slot p mod SP_W; 64 positions, since the four waves of a CU share its
+ * LDS).  The ring is filled in chunks of SP_C positions, two per batch: a
+ * batch is issued into registers (SpStage) and written to LDS SP_K steps
+ * later, so the load latency overlaps the steps.  A target outside the ring
+ * (a long jump) is read from global memory in a wave-uniform branch that
+ * waits for its loads at once: a miss load left in flight would make every
+ * later ring read wait for the batch in flight too. */
 #ifndef SP_W
-#define SP_W    64u
+#define SP_W    64u                     /* positions per lane ring           */
 #endif
-#define SP_C    16u
+#define SP_C    16u                     /* positions per chunk               */
 #ifndef SP_K
-#define SP_K    4u
+#define SP_K    4u                      /* steps between batches             */
 #endif
-#define SP_RS   (SP_W * 8u + 16u)
-#define SP_SS   (SP_W + 16u)
+#define SP_RS   (SP_W * 8u + 16u)       /* rec ring row bytes (padded)       */
+#define SP_SS   (SP_W + 16u)            /* byte ring row bytes (padded)      */
+#define SP_VMCNT0 0x0f70                /* s_waitcnt vmcnt(0), gfx9 encoding  */
+
+typedef uint32_t sp_v4 __attribute__((ext_vector_type(4)));
+struct SpStage { sp_v4 a, b, c, d, e, f, g, h, s; };
 
 /* ST: stream mode (compiled out of the block-mode instantiation) */
 template <bool ST>
@@ -2072,21 +1871,21 @@ __global__ __launch_bounds__(64) void k_pspec(PSplitArgs a)
     /* the ring holds positions [vlo, rdy) in slots p mod SP_W; np chunks
      * from rdy on are in flight in st0/st1 */
     uint32_t rdy = s.cur & ~(SP_C - 1), vlo = rdy, np = 0;
-    PrStage st0, st1;
+    SpStage st0, st1;
 #define SP_LD(st_, q_)                                                                 \
     do {                                                                               \
-        const pr_v4* g_ = (const pr_v4*) (rec + (q_));                                 \
+        const sp_v4* g_ = (const sp_v4*) (rec + (q_));                                 \
         st_.a = g_[0]; st_.b = g_[1]; st_.c = g_[2]; st_.d = g_[3];                    \
         st_.e = g_[4]; st_.f = g_[5]; st_.g = g_[6]; st_.h = g_[7];                    \
-        st_.s = *(const pr_v4*) (src + (q_));                                          \
+        st_.s = *(const sp_v4*) (src + (q_));                                          \
     } while (0)
 #define SP_ST(st_, q_)                                                                 \
     do {                                                                               \
         const uint32_t w_ = (q_) & (SP_W - 1);                                         \
-        pr_v4* d_ = (pr_v4*) (rr + w_ * 8);                                            \
+        sp_v4* d_ = (sp_v4*) (rr + w_ * 8);                                            \
         d_[0] = st_.a; d_[1] = st_.b; d_[2] = st_.c; d_[3] = st_.d;                    \
         d_[4] = st_.e; d_[5] = st_.f; d_[6] = st_.g; d_[7] = st_.h;                    \
-        *(pr_v4*) (sr + w_) = st_.s;                                                   \
+        *(sp_v4*) (sr + w_) = st_.s;                                                   \
     } while (0)
 #define SP_ISSUE()                                                                     \
     do {                                                                               \
@@ -2152,7 +1951,7 @@ __global__ __launch_bounds__(64) void k_pspec(PSplitArgs a)
             if (__ballot(mis)) {
                 SP_MISS(n1c, r1, c1);
                 SP_MISS(n2c, r2, c2);
-                __builtin_amdgcn_s_waitcnt(PR_VMCNT0);
+                __builtin_amdgcn_s_waitcnt(SP_VMCNT0);
             }
             uint32_t ex, ey;
             if (ps_decide<ST>(x, s, ds, n1, r1, c1, r2, c2, ex, ey)) out[ne++] = make_uint2(ex, ey);
@@ -3871,6 +3670,21 @@ extern "C" uint32_t jdk_chains_bytes(int level)
     return level >= K2S_FROM ? 10u : 4u;
 }
 
+/* k_match's link walk over `grid` 16 K-position sub-blocks.  The greedy
+ * levels use getmatch1 :2335: initial threshold MINMATCH, so a record only
+ * matters when longer than 3 */
+static void launch_match(hipStream_t st, uint32_t grid, const uint8_t* in, uint64_t n, uint32_t bs,
+                         const uint16_t* prev4, const uint16_t* prev3, uint64_t* rec, const JdLevel& lv,
+                         int level, bool lazy)
+{
+    if (level >= 8)
+        JDPROF_RUN(JDK_MATCH, st, (k_match<true><<<grid, 1024, 0, st>>>(in, n, bs, prev4, prev3, rec, lv.chain, lv.nice,
+                                                                        lazy ? 3 : 4, lazy ? 1 : 0)));
+    else
+        JDPROF_RUN(JDK_MATCH, st, (k_match<false><<<grid, 1024, 0, st>>>(in, n, bs, prev4, prev3, rec, lv.chain, lv.nice,
+                                                                         lazy ? 3 : 4, lazy ? 1 : 0)));
+}
+
 extern "C" int jdk_deflate_launch(const JdDeflateLaunch* L)
 {
     hipStream_t st = (hipStream_t) L->stream;
@@ -3882,61 +3696,46 @@ extern "C" int jdk_deflate_launch(const JdDeflateLaunch* L)
     } else {
         const JdLevel lv = jd_level(L->level);
         const bool lazy = L->level >= 6;
+        /* the lazy levels have the split parse only */
+        if (lazy && !L->plist) return -1;
         uint16_t* prev4 = L->chains;
         uint16_t* prev3 = L->chains + L->nslots;
-        if (L->level < K2S_FROM) {
-        /* the hash-4 links and k_match's link walk (the slice walk below
-         * measured slower at level 6: DESIGN.md §9 round 6) */
-        JDPROF_RUN(JDK_CHAINS4, st, (k_chains<4><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, nullptr, jd_chains_flag(0), nullptr, 0,
-                                                                          nullptr, 0)));
-        if (test_badlinks()) k_badlinks<<<(uint32_t) ((L->n + 255) / 256), 256, 0, st>>>(prev4, nullptr, 0, L->n, L->bs);
-        if (lazy)
-            JDPROF_RUN(JDK_CHAINS3, st, (k_chains<3><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev3, L->dsg, jd_chains_flag(0), nullptr, 0,
-                                                                          nullptr, 0)));
-        {
-            const uint32_t nsub = (L->bs + K2_SR - 1) / K2_SR;
-            /* greedy levels use getmatch1 :2335: initial threshold MINMATCH, so
-             * a record only matters when longer than 3 */
-            if (L->level >= 8)
-                JDPROF_RUN(JDK_MATCH, st, (k_match<true><<<nb * nsub, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, prev3,
-                                                                                     L->rec, lv.chain, lv.nice,
-                                                                                     lazy ? 3 : 4, lazy ? 1 : 0)));
-            else
-                JDPROF_RUN(JDK_MATCH, st, (k_match<false><<<nb * nsub, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, prev3,
-                                                                                      L->rec, lv.chain, lv.nice,
-                                                                                      lazy ? 3 : 4, lazy ? 1 : 0)));
-        }
-        } else {
-        /* the slices: S after 16 entries of padding (a chunk load may start
-         * below a block's first entry), W 4-byte aligned after it */
-        uint16_t* sl_s = L->chains + 2 * L->nslots + 16;
-        uint32_t* sl_w = (uint32_t*) (L->chains + 3 * L->nslots + 32);
-        SlOut<true> so;
-        so.s = sl_s; so.w = sl_w; so.chain = lv.chain;
-        JDPROF_RUN(JDK_CHAINS4, st, (k_chains<4, false, true><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, nullptr,
-                                                                                  jd_chains_flag(0), nullptr, 0,
-                                                                                  nullptr, 0, so)));
-        if (test_badlinks())
-            k_badlinks<<<(uint32_t) ((L->n + 255) / 256), 256, 0, st>>>(prev4, sl_w, lv.chain, L->n, L->bs);
-        if (lazy)
-            JDPROF_RUN(JDK_CHAINS3, st, (k_chains<3><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev3, L->dsg, jd_chains_flag(0), nullptr, 0,
-                                                                          nullptr, 0)));
         const uint32_t nsub = (L->bs + K2_SR - 1) / K2_SR;
-        if (L->level >= 8)
-            JDPROF_RUN(JDK_MATCH, st, (k_match_sl<true, K2S_NT><<<nb * nsub, K2S_NT, 0, st>>>(
-                                          L->in, L->n, L->bs, sl_s, sl_w, prev3, L->rec, lv.chain, lv.nice,
-                                          lazy ? 1 : 0)));
-        else
-            JDPROF_RUN(JDK_MATCH, st, (k_match_sl<false, K2S_NT><<<nb * nsub, K2S_NT, 0, st>>>(
-                                          L->in, L->n, L->bs, sl_s, sl_w, prev3, L->rec, lv.chain, lv.nice,
-                                          lazy ? 1 : 0)));
+        if (L->level < K2S_FROM) {
+            /* the hash-4 links and k_match's link walk (the slice walk below
+             * measured slower at level 6: DESIGN.md §9 round 6) */
+            JDPROF_RUN(JDK_CHAINS4, st, (k_chains<4><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, nullptr, jd_chains_flag(0), nullptr, 0,
+                                                                          nullptr, 0)));
+            if (test_badlinks()) k_badlinks<<<(uint32_t) ((L->n + 255) / 256), 256, 0, st>>>(prev4, nullptr, 0, L->n, L->bs);
+            if (lazy)
+                JDPROF_RUN(JDK_CHAINS3, st, (k_chains<3><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev3, L->dsg, jd_chains_flag(0), nullptr, 0,
+                                                                              nullptr, 0)));
+            launch_match(st, nb * nsub, L->in, L->n, L->bs, prev4, prev3, L->rec, lv, L->level, lazy);
+        } else {
+            /* the slices: S after 16 entries of padding (a chunk load may start
+             * below a block's first entry), W 4-byte aligned after it */
+            uint16_t* sl_s = L->chains + 2 * L->nslots + 16;
+            uint32_t* sl_w = (uint32_t*) (L->chains + 3 * L->nslots + 32);
+            SlOut<true> so;
+            so.s = sl_s; so.w = sl_w; so.chain = lv.chain;
+            JDPROF_RUN(JDK_CHAINS4, st, (k_chains<4, false, true><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev4, nullptr,
+                                                                                      jd_chains_flag(0), nullptr, 0,
+                                                                                      nullptr, 0, so)));
+            if (test_badlinks())
+                k_badlinks<<<(uint32_t) ((L->n + 255) / 256), 256, 0, st>>>(prev4, sl_w, lv.chain, L->n, L->bs);
+            if (lazy)
+                JDPROF_RUN(JDK_CHAINS3, st, (k_chains<3><<<nb, 1024, 0, st>>>(L->in, L->n, L->bs, prev3, L->dsg, jd_chains_flag(0), nullptr, 0,
+                                                                              nullptr, 0)));
+            if (L->level >= 8)
+                JDPROF_RUN(JDK_MATCH, st, (k_match_sl<true, K2S_NT><<<nb * nsub, K2S_NT, 0, st>>>(
+                                              L->in, L->n, L->bs, sl_s, sl_w, prev3, L->rec, lv.chain, lv.nice,
+                                              lazy ? 1 : 0)));
+            else
+                JDPROF_RUN(JDK_MATCH, st, (k_match_sl<false, K2S_NT><<<nb * nsub, K2S_NT, 0, st>>>(
+                                              L->in, L->n, L->bs, sl_s, sl_w, prev3, L->rec, lv.chain, lv.nice,
+                                              lazy ? 1 : 0)));
         }
-        ParseArgs pa;
-        pa.rec = L->rec; pa.prev4 = prev4; pa.in = L->in; pa.n = L->n; pa.bs = L->bs;
-        pa.nblocks = nb; pa.tokens = L->tokens;
-        pa.dbinfo = L->dbinfo; pa.good = lv.good; pa.lzcap = lv.lzcap;
-        pa.nice = lv.nice; pa.half = lv.chain >> 1; pa.lazy = lazy;
-        if (lazy && L->plist) {
+        if (lazy) {
             PSplitArgs ps;
             memset(&ps, 0, sizeof(ps));
             ps.rec = L->rec; ps.prev4 = prev4; ps.in = L->in; ps.n = L->n; ps.bs = L->bs;
@@ -3954,10 +3753,13 @@ extern "C" int jdk_deflate_launch(const JdDeflateLaunch* L)
             JDPROF_RUN(JDK_PSYNC, st, (k_psync<<<ng, 64, 0, st>>>(ps)));
             JDPROF_RUN(JDK_PJOIN, st, (k_pjoin<false><<<nb, 64, 0, st>>>(ps)));
         } else {
+            ParseArgs pa;
+            pa.rec = L->rec; pa.in = L->in; pa.n = L->n; pa.bs = L->bs;
+            pa.nblocks = nb; pa.tokens = L->tokens; pa.dbinfo = L->dbinfo; pa.lzcap = lv.lzcap;
             JDPROF_RUN(JDK_PARSE, st, (k_parse<<<(nb + 63) / 64, 64, 0, st>>>(pa)));
         }
         EmitArgs ea;
-        ea.tokens = pa.tokens; ea.dbinfo = L->dbinfo; ea.n = L->n; ea.bs = L->bs;
+        ea.tokens = L->tokens; ea.dbinfo = L->dbinfo; ea.n = L->n; ea.bs = L->bs;
         ea.nblocks = nb; ea.slotcap = L->slotcap; ea.level = L->level;
         ea.fixed = L->flags & 1u; ea.lastfinal = L->lastfinal;
         ea.stage = L->stage; ea.csize = L->csize; ea.sdb = nullptr;
@@ -4018,14 +3820,7 @@ extern "C" int jdk_deflate_stream_launch(const JdStreamLaunch* L)
                                                                                   L->last3, L->dsize, nullptr, 0)));
         }
         const uint32_t nsub = (uint32_t) ((n + K2_SR - 1) / K2_SR);
-        if (L->level >= 8)
-            JDPROF_RUN(JDK_MATCH, st, (k_match<true><<<nsub, 1024, 0, st>>>(L->in, n, (uint32_t) n, prev4, prev3,
-                                                                            L->rec, lv.chain, lv.nice,
-                                                                            lazy ? 3 : 4, lazy ? 1 : 0)));
-        else
-            JDPROF_RUN(JDK_MATCH, st, (k_match<false><<<nsub, 1024, 0, st>>>(L->in, n, (uint32_t) n, prev4, prev3,
-                                                                             L->rec, lv.chain, lv.nice,
-                                                                             lazy ? 3 : 4, lazy ? 1 : 0)));
+        launch_match(st, nsub, L->in, n, (uint32_t) n, prev4, prev3, L->rec, lv, L->level, lazy);
         /* lazy: lists for both doshort values; greedy: doshort plays no part */
         if (hipMemsetD32Async((hipDeviceptr_t) L->dsg, lazy ? 3 : 1, nb, st) != hipSuccess) return -1;
         PSplitArgs ps;

@@ -324,8 +324,9 @@ int deflate_dev(Engine& e, const uint8_t* d_in, uint64_t n, uint32_t bs, int lev
     const uint32_t cb = (uint32_t) (nb < JD_CHUNK_BLOCKS ? nb : JD_CHUNK_BLOCKS);
     const uint32_t slot = slotcap_for(bs);
     const uint64_t slots = (uint64_t) cb * bs;
-    /* levels 6-9: the segment-split parse (k_pspec/k_psync/k_pjoin); levels
-     * 1-5: the one-lane-per-block greedy k_parse */
+    /* levels 6-9: the segment-split parse (k_pspec/k_psync/k_pjoin), whose
+     * lists jdk_deflate_launch requires there; levels 1-5: the
+     * one-lane-per-block greedy k_parse */
     const bool split = level >= 6;
     const uint32_t pcap = jdk_pcap(bs);
     const int r = dscratch(e.ds, cb, bs, level, split);

@@ -33,7 +33,8 @@ typedef struct {
     const uint64_t* base;   /* device: offset of this chunk (NULL = 0)   */
     uint8_t* out;           /* device: compacted output (may be NULL)    */
     uint64_t outcap;
-    /* split lazy parse (levels 6-9; all NULL: the one-lane-per-block parse) */
+    /* split lazy parse: required at levels 6-9 (the launch fails without
+     * plist), unused at the greedy levels 1-5 */
     uint64_t* plist;        /* device: nblocks * JD_PSEG * pcap entries   */
     uint32_t* pcount;       /* device: nblocks * JD_PSEG                  */
     uint32_t* psync;        /* device: nblocks * JD_PSEG * 2              */

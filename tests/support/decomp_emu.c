@@ -3,8 +3,8 @@
  * deflater (TEST SUPPORT ONLY): k_chains (per-position chain links),
  * k_match (one chain walk per position with a running threshold of 2,
  * recording the full- and half-budget results and the 3-byte candidate) and
- * k_parse (lazy parse over the records, including the held step whose
- * threshold reaches `nice`).  tests/test_decomposition.py checks that this
+ * ps_decide (the lazy step over the records, including the held step whose
+ * threshold reaches `nice`), walked serially over the block.  tests/test_decomposition.py checks that this
  * decomposition reproduces the oracle's token stream, i.e. that the
  * restructuring argued in DESIGN.md is exact, without a GPU.
  *
