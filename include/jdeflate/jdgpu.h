@@ -298,6 +298,87 @@ JDEFLATE_API int jdgpu_inflate_flushed(const uint8* src, uint64 srclen, uint64 r
                                        uint64* consumed, int32* error, uint32* crc,
                                        uint32* adler);
 
+/* ---- BGZF container (the indexed form) ------------ */
+/*
+ * BGZF is the blocked gzip of htslib, bgzip, BAM and tabix: a series of gzip
+ * members of at most 65536 bytes, each a complete deflate stream of one
+ * independent block with its own size (BSIZE, in an FEXTRA 'BC' subfield),
+ * CRC-32 and ISIZE, ended by a fixed empty member of 28 bytes.  Member i
+ * holds what the reference writes for a fresh deflator given block i with
+ * DEFLT_END; a block whose stream a member cannot hold (more than 65510
+ * bytes: random data at level 1) is written as one final stored block, as
+ * htslib does.  blocksize: a multiple of 16, at most 65280 (htslib's value).
+ */
+/* per-member codes of the BGZF inflate, after the inflator.h codes and
+ * JDGPU_EBLOCKOVERFLOW */
+#define JDGPU_EMEMBERSIZE 10     /* decoded size differs from ISIZE          */
+#define JDGPU_EMEMBERCRC  11     /* CRC-32 differs from the trailer's        */
+
+/* worst-case size of the BGZF output for n input bytes (0: bad blocksize) */
+JDEFLATE_API uint64 jdgpu_bgzf_bound(uint64 n, uint32 blocksize);
+
+/*
+ * Device-resident BGZF deflate.  d_in: n bytes (16-byte aligned); d_out:
+ * outcap bytes, any alignment.  d_boffsets (device, ceil(n / blocksize)
+ * entries, or NULL) receives the member offsets, the high 48 bits of BGZF
+ * virtual offsets; *d_total (device) the output size, EOF marker included
+ * (n = 0: the marker alone).  A member that would end past outcap is not
+ * written: *d_total > outcap tells.  Asynchronous, as jdgpu_deflate_device.
+ */
+JDEFLATE_API int jdgpu_bgzf_deflate_device(const void* d_in, uint64 n, uint32 blocksize, int level,
+                                           uint32 flags, void* d_out, uint64 outcap,
+                                           uint64* d_boffsets, uint64* d_total, void* stream);
+/* Host buffers: returns the output size or a negative error (JDGPU_ECAP when
+ * cap is too small); boffsets (host, optional) as above. */
+JDEFLATE_API int64 jdgpu_bgzf_deflate(const uint8* src, uint64 n, uint32 blocksize, int level,
+                                      uint32 flags, uint8* dst, uint64 cap, uint64* boffsets);
+
+/*
+ * Index of the members of an arbitrary BGZF buffer, on the chain from offset
+ * 0 to the buffer's end.  A member is valid when 1f 8b 08 is present, FLG is
+ * exactly 0x04, XLEN >= 6, the extra field's subfields (others may come
+ * first) hold a 'B','C' subfield of length 2, BSIZE + 1 >= XLEN + 20 and the
+ * member ends within the buffer.  Per member: its offset, its payload's
+ * offset (member + 12 + XLEN) and size (BSIZE + 1 - XLEN - 20), and the
+ * trailer's ISIZE and CRC-32; *nblocks members; *eof = 1 when the last one is
+ * the EOF marker (its absence is no error).  Returns 0; JDGPU_EDATA when the
+ * chain steps onto bytes that are no valid member (the members before are
+ * indexed: the last good one is at moff[*nblocks - 1]); JDGPU_ECAP when
+ * there are more than maxblocks members (or, on the device, more header
+ * candidates than the scratch for maxblocks holds: 2 * maxblocks + 1024).
+ * The device form (d_in 16-byte aligned; arrays of maxblocks entries in
+ * device memory) tests every byte position, links the candidates and
+ * resolves the chain by pointer doubling -- depth logarithmic in the number
+ * of members -- and equals the host form, a serial walk without a GPU, on
+ * the same bytes.  It synchronises the stream.
+ */
+JDEFLATE_API int jdgpu_bgzf_index_device(const void* d_in, uint64 inlen, uint32 maxblocks,
+                                         uint64* d_moff, uint64* d_poff, uint32* d_psize,
+                                         uint32* d_isize, uint32* d_crc, uint32* d_nblocks,
+                                         uint32* d_eof, void* stream);
+JDEFLATE_API int jdgpu_bgzf_index(const uint8* src, uint64 srclen, uint32 maxblocks, uint64* moff,
+                                  uint64* poff, uint32* psize, uint32* isize, uint32* crc,
+                                  uint32* nblocks, uint32* eof);
+
+/*
+ * BGZF inflate: index, block-parallel decode, gather, verify.  The members'
+ * data is written end to end into d_out (16-byte aligned for the path without
+ * a copy: every member but the last of one ISIZE, a multiple of 16, as written
+ * here), *d_total (device) receives its size, d_errors (device, maxblocks
+ * entries) per member 0, an inflator.h code, JDGPU_EBLOCKOVERFLOW,
+ * JDGPU_EMEMBERSIZE or JDGPU_EMEMBERCRC.  Returns 0, JDGPU_EDATA when the
+ * index or any member failed, JDGPU_ECAP (maxblocks or outcap too small).
+ * Synchronises the stream.
+ */
+JDEFLATE_API int jdgpu_bgzf_inflate_device(const void* d_in, uint64 inlen, void* d_out,
+                                           uint64 outcap, uint64* d_total, int32* d_errors,
+                                           uint32 maxblocks, void* stream);
+/* Host buffers; the members are walked on the host.  errors (optional) needs
+ * as many entries as jdgpu_bgzf_index counts members. */
+JDEFLATE_API int jdgpu_bgzf_inflate(const uint8* src, uint64 srclen, uint8* dst, uint64 cap,
+                                    uint64* produced, uint32* nblocks, uint32* eof,
+                                    int32* errors);
+
 /* ---- diagnostics (tests and the benchmark) ---------------------------- */
 
 /* Per-kernel timing with HIP events recorded on each kernel's stream.

@@ -10,6 +10,8 @@ from .engine import (  # noqa: F401
     EXPORTS, Inflator, available, bound, corpus_mixed, corpus_text, deflate_blocks,
     deflate_device, deflate_stream, inflate_blocks, inflate_device, inflate_stream,
     deflate_multi, inflate_multi,
+    BGZF_BLOCKSIZE, BGZF_EOF, BgzfError, bgzf_bound, bgzf_compress, bgzf_decompress, bgzf_index,
+    bgzf_deflate_device, bgzf_index_device, bgzf_inflate_device,
     load_library, nblocks,
     prof_enable, prof_read, KERNELS, ZStrm, checksums, crc32_combine,
 )

@@ -20,6 +20,7 @@
  * HBM-bound: the block is read once (16-byte loads).
  */
 #include "jd_device.h"
+#include "jd_bgzf.h"
 #include "jd_kernels.h"
 #include "jd_prof.h"
 
@@ -144,6 +145,79 @@ __global__ __launch_bounds__(256) void k_checksum(const uint8_t* __restrict__ in
         out[3 * (uint64_t) b + 1] = (uint32_t) (pa[0] % 65521u);
         out[3 * (uint64_t) b + 2] = (uint32_t) (pb[0] % 65521u);
     }
+}
+
+/* ------------------------------------------------------------------------ */
+/* The BGZF verify scan (jd_bgzf.h): k_checksum's CRC with per-member lengths
+ * and a slot stride.  Member b's decoded bytes are in + b * stride (16-byte
+ * aligned), usize[b] of them.  gzip's CRC-32 is ~R(0xFFFFFFFF, D) =
+ * ~(shift(0xFFFFFFFF, |D|) ^ R(0, D)).  Where the decoder left err[b] = 0 it
+ * becomes esize on a size mismatch with the trailer's ISIZE, else ecrc on a
+ * CRC mismatch. */
+__global__ __launch_bounds__(256) void k_checksum_members(const uint8_t* __restrict__ in, uint32_t stride,
+                                                          const uint32_t* __restrict__ usize,
+                                                          const uint32_t* __restrict__ isize,
+                                                          const uint32_t* __restrict__ tcrc,
+                                                          const uint32_t* __restrict__ shiftm,
+                                                          int32_t* __restrict__ err, int32_t esize,
+                                                          int32_t ecrc)
+{
+    __shared__ uint32_t tab[4][256];
+    __shared__ uint32_t sm[17][32];
+    __shared__ uint32_t pc[CK_T];
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    if (err[b]) return;
+    const uint32_t len = min(usize[b], stride);
+    if (len != isize[b]) {
+        if (tid == 0) err[b] = esize;
+        return;
+    }
+    const uint8_t* blk = in + (uint64_t) b * stride;
+    const uint32_t P = ((stride + CK_T - 1) / CK_T + 15) & ~15u;
+    const uint32_t p0 = min(len, tid * P), p1 = min(len, p0 + P);
+    {
+        uint32_t c = tid;
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
+        tab[0][tid] = c;
+    }
+    for (uint32_t i = tid; i < 17 * 32; i += CK_T) sm[i >> 5][i & 31] = shiftm[i];
+    __syncthreads();
+    for (int k = 1; k < 4; k++) {
+        const uint32_t c = tab[k - 1][tid];
+        tab[k][tid] = (c >> 8) ^ tab[0][c & 0xff];
+        __syncthreads();
+    }
+    uint32_t crc = 0, s = 0, w = 0;
+    uint32_t i = p0;
+    for (; i + 16 <= p1; i += 16) {
+        const uint4 u = *(const uint4*) (blk + i);
+        const uint32_t x[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) ck_word(tab, crc, s, w, x[q]);
+    }
+    for (; i < p1; i++) crc = (crc >> 8) ^ tab[0][(crc ^ blk[i]) & 0xff];
+    pc[tid] = crc;
+    __syncthreads();
+    for (uint32_t h = 1; h < CK_T; h <<= 1) {
+        if ((tid & (2 * h - 1)) == 0) {
+            const uint32_t r0 = min(len, (tid + h) * P), r1 = min(len, (tid + 2 * h) * P);
+            pc[tid] = crc_shift(sm, pc[tid], r1 - r0) ^ pc[tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && ~(crc_shift(sm, 0xffffffffu, len) ^ pc[0]) != tcrc[b]) err[b] = ecrc;
+}
+
+extern "C" int jdk_checksum_members_launch(const uint8_t* in, uint32_t stride, uint32_t nblocks,
+                                           const uint32_t* usize, const uint32_t* isize,
+                                           const uint32_t* crc, const uint32_t* shiftm, int32_t* err,
+                                           int32_t esize, int32_t ecrc, void* stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    if (!nblocks) return 0;
+    JDPROF_RUN(JDK_BGZF_VERIFY, st, (k_checksum_members<<<nblocks, CK_T, 0, st>>>(in, stride, usize, isize, crc, shiftm,
+                                                                             err, esize, ecrc)));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -3417,7 +3417,7 @@ __global__ __launch_bounds__(EM_T) __attribute__((amdgpu_waves_per_eu(EM_WPE))) 
     /* endstream :610-654: empty stored block, BFINAL per flush mode */
     if (tid == 0) {
         const bool last = b + 1 == a.nblocks;
-        em_put(s, (last && a.lastfinal) ? 1 : 0, 1);
+        em_put(s, ((last && a.lastfinal) || a.lastfinal == 2) ? 1 : 0, 1);
         em_put(s, 0, 2);
         s.bp = (s.bp + 7) & ~7u;
         em_put(s, 0x0000, 16);
@@ -3458,7 +3458,7 @@ __global__ __launch_bounds__(256) void k_stored(const uint8_t* __restrict__ in,
     }
     if (threadIdx.x == 0) {
         const bool last = b + 1 == nblocks;
-        dst[o] = (last && lastfinal) ? 1 : 0;
+        dst[o] = ((last && lastfinal) || lastfinal == 2) ? 1 : 0;
         dst[o + 1] = 0; dst[o + 2] = 0; dst[o + 3] = 0xff; dst[o + 4] = 0xff;
         csize[b] = o + 5;
     }
@@ -3765,10 +3765,31 @@ extern "C" int jdk_deflate_launch(const JdDeflateLaunch* L)
         ea.stage = L->stage; ea.csize = L->csize; ea.sdb = nullptr;
         JDPROF_RUN(JDK_EMIT, st, (k_emit<<<nb, EM_T, 0, st>>>(ea)));
     }
-    JDPROF_RUN(JDK_SCAN, st, (k_scan<<<1, 1024, 0, st>>>(L->csize, nb, L->coff, L->total, L->base)));
-    if (L->out)
+    /* no coff: the caller lays the blocks out itself (BGZF members) */
+    if (L->coff)
+        JDPROF_RUN(JDK_SCAN, st, (k_scan<<<1, 1024, 0, st>>>(L->csize, nb, L->coff, L->total, L->base)));
+    if (L->out && L->coff)
         JDPROF_RUN(JDK_COMPACT, st, (k_compact<<<nb, 256, 0, st>>>(L->stage, L->slotcap, L->csize,
                                                                     L->coff, L->out, L->outcap)));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* k_scan and k_compact for the callers with sizes of their own (jd_bgzf.h) */
+extern "C" int jdk_scan_launch(const uint32_t* sz, uint32_t nb, uint64_t* off, uint64_t* total,
+                               const uint64_t* base, void* stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    JDPROF_RUN(JDK_SCAN, st, (k_scan<<<1, 1024, 0, st>>>(sz, nb, off, total, base)));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int jdk_compact_launch(const uint8_t* stage, uint32_t slotcap, const uint32_t* sz,
+                                  const uint64_t* off, uint32_t nb, uint8_t* out, uint64_t outcap,
+                                  void* stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    if (!nb) return 0;
+    JDPROF_RUN(JDK_COMPACT, st, (k_compact<<<nb, 256, 0, st>>>(stage, slotcap, sz, off, out, outcap)));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "jd_bgzf.h"
 #include "jd_crc.h"
 #include "jd_kernels.h"
 #include "jd_prof.h"
@@ -168,6 +169,14 @@ struct IScratch {
     DevBuf irec, inrec, ifb;
 };
 
+/* BGZF workspace: member sizes, the index and its scratch, decode slots */
+struct BScratch {
+    DevBuf msize;
+    DevBuf wcnt, woff, ctotal, cpos, cnext, cxl, jd;
+    DevBuf moff, poff, psize, isize, crc, res;
+    DevBuf slots, gsize, goff;
+};
+
 /* single-window stream workspace */
 struct SScratch {
     DevBuf chains, rec, tokens, last3, plist, pcount, psync, dsg, dbinfo;
@@ -182,6 +191,7 @@ struct Engine {
     hipStream_t stream = nullptr;
     DScratch ds;
     IScratch is;
+    BScratch bz;
     DevBuf csize, coff, total, zero;
     DevBuf hin, hout, hsz, hoff, hus, herr, hused;   /* host-API staging */
     DevBuf shiftm, ck;                                /* checksums         */
@@ -313,9 +323,16 @@ int dscratch(DScratch& x, uint32_t cb, uint32_t bs, int level, bool split)
 
 /* deflate a device-resident input in launch chunks of up to
  * JD_CHUNK_BLOCKS blocks; caller holds the lock */
+/* bz: every block final and framed as a BGZF member (d_coffs then receives
+ * the member offsets), the EOF marker after the last */
+struct BgzfEnc {
+    uint32_t sfull, slast;      /* jd_bgzf.h JdBgzfFrame */
+};
+
 int deflate_dev(Engine& e, const uint8_t* d_in, uint64_t n, uint32_t bs, int level,
                 uint32_t flags, int lastflush, uint8_t* d_out, uint64_t outcap,
-                uint32_t* d_csizes, uint64_t* d_coffs, uint64_t* d_total, hipStream_t st)
+                uint32_t* d_csizes, uint64_t* d_coffs, uint64_t* d_total, hipStream_t st,
+                const BgzfEnc* bz = nullptr)
 {
     if (!valid_bs(bs) || level < 0 || level > 9) return JDGPU_EINVAL;
     if (lastflush != 1 && lastflush != 2) return JDGPU_EINVAL;
@@ -337,6 +354,8 @@ int deflate_dev(Engine& e, const uint8_t* d_in, uint64_t n, uint32_t bs, int lev
     uint32_t* csz = d_csizes ? d_csizes : e.csize.as<uint32_t>();
     uint64_t* cof = d_coffs ? d_coffs : e.coff.as<uint64_t>();
     uint64_t* tot = d_total ? d_total : e.total.as<uint64_t>();
+    if (bz && (!e.bz.msize.ensure((uint64_t) cb * 4 + 64) || !e.ck.ensure((uint64_t) cb * 12 + 64)))
+        return JDGPU_EOOM;
     DScratch& x = e.ds;
     for (uint64_t b0 = 0; b0 < nb; b0 += cb) {
         const uint32_t k = (uint32_t) (nb - b0 < cb ? nb - b0 : cb);
@@ -373,7 +392,38 @@ int deflate_dev(Engine& e, const uint8_t* d_in, uint64_t n, uint32_t bs, int lev
             L.pord = x.pord.as<uint32_t>();
         }
         L.stream = st;
+        if (bz) {
+            L.lastfinal = 2;
+            L.coff = nullptr;
+            L.out = nullptr;
+        }
         if (jdk_deflate_launch(&L)) return JDGPU_ENODEV;
+        if (bz) {
+            if (jdk_checksum_launch(L.in, L.n, bs, e.shiftm.as<uint32_t>(), e.ck.as<uint32_t>(), st))
+                return JDGPU_ENODEV;
+            JdBgzfFrame F;
+            memset(&F, 0, sizeof(F));
+            F.in = L.in;
+            F.n = L.n;
+            F.bs = bs;
+            F.nblocks = k;
+            F.stage = L.stage;
+            F.slotcap = slot;
+            F.csize = L.csize;
+            F.ck = e.ck.as<uint32_t>();
+            F.sfull = bz->sfull;
+            F.slast = bz->slast;
+            F.lastb = b0 + k == nb ? k - 1 : 0xffffffffu;
+            F.eof = b0 + k == nb;
+            F.msize = e.bz.msize.as<uint32_t>();
+            F.moff = cof + b0;
+            F.total = tot;
+            F.base = L.base;
+            F.out = d_out;
+            F.outcap = outcap;
+            F.stream = st;
+            if (jdk_bgzf_frame_launch(&F)) return JDGPU_ENODEV;
+        }
     }
     return 0;
 }
@@ -1037,6 +1087,397 @@ JDEFLATE_API int jdgpu_inflate(const uint8* src, uint64 srclen, const uint32* cs
     std::lock_guard<std::mutex> g(e.mu);
     return inflate_host(e, src, srclen, csizes, nblocks, blocksize, dst,
                         (uint64_t) nblocks * blocksize, usizes, errors, nullptr, 0);
+}
+
+/* ---- BGZF container (jdgpu.h; jd_bgzf.h) ------------------------------- */
+
+static bool bgzf_bs(uint32_t bs) { return bs >= 16 && bs <= JD_BGZF_MAXBS && (bs & 15) == 0; }
+
+static uint64_t bgzf_bound(uint64_t n, uint32_t bs)
+{
+    const uint64_t nb = (n + bs - 1) / bs;
+    uint64_t per = slotcap_for(bs);
+    /* a payload past JD_BGZF_MAXPAY is replaced by the stored block */
+    if (per > JD_BGZF_MAXPAY) per = JD_BGZF_MAXPAY;
+    if (per < bs + 5u) per = bs + 5u;
+    return nb * (per + JD_BGZF_FRAME) + JD_BGZF_EOFLEN;
+}
+
+JDEFLATE_API uint64 jdgpu_bgzf_bound(uint64 n, uint32 blocksize)
+{
+    return bgzf_bs(blocksize) ? bgzf_bound(n, blocksize) : 0;
+}
+
+/* caller holds the lock */
+static int bgzf_deflate_dev(Engine& e, const uint8_t* d_in, uint64_t n, uint32_t bs, int level,
+                            uint32_t flags, uint8_t* d_out, uint64_t outcap, uint64_t* d_boff,
+                            uint64_t* d_total, hipStream_t st)
+{
+    if (!bgzf_bs(bs) || level < 0 || level > 9 || (flags & ~1u) || !d_out) return JDGPU_EINVAL;
+    if (n && (!d_in || ((uintptr_t) d_in & 15))) return JDGPU_EINVAL;
+    if (!n) {
+        /* the marker alone */
+        if (!d_total && !e.total.ensure(64)) return JDGPU_EOOM;
+        JdBgzfFrame F;
+        memset(&F, 0, sizeof(F));
+        F.eof = 1;
+        F.lastb = 0xffffffffu;
+        F.total = d_total ? d_total : e.total.as<uint64_t>();
+        F.out = d_out;
+        F.outcap = outcap;
+        F.stream = st;
+        if (hipMemsetAsync(F.total, 0, 8, st) != hipSuccess || jdk_bgzf_frame_launch(&F)) return JDGPU_ENODEV;
+        return 0;
+    }
+    BgzfEnc bz;
+    const uint64_t lastlen = n - (n - 1) / bs * bs;
+    bz.sfull = jdcrc_shift(0xffffffffu, bs);
+    bz.slast = jdcrc_shift(0xffffffffu, lastlen);
+    return deflate_dev(e, d_in, n, bs, level, flags, 1, d_out, outcap, nullptr, d_boff, d_total, st, &bz);
+}
+
+JDEFLATE_API int jdgpu_bgzf_deflate_device(const void* d_in, uint64 n, uint32 blocksize, int level,
+                                           uint32 flags, void* d_out, uint64 outcap,
+                                           uint64* d_boffsets, uint64* d_total, void* stream)
+{
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    if (!ready(e)) return JDGPU_ENODEV;
+    hipStream_t st = stream ? (hipStream_t) stream : e.stream;
+    order(e, st);
+    const int r = bgzf_deflate_dev(e, (const uint8_t*) d_in, n, blocksize, level, flags, (uint8_t*) d_out,
+                                   outcap, (uint64_t*) d_boffsets, (uint64_t*) d_total, st);
+    mark(e, st);
+    return r;
+}
+
+JDEFLATE_API int64 jdgpu_bgzf_deflate(const uint8* src, uint64 n, uint32 blocksize, int level,
+                                      uint32 flags, uint8* dst, uint64 cap, uint64* boffsets)
+{
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    if (!ready(e)) return JDGPU_ENODEV;
+    if (!bgzf_bs(blocksize) || (!src && n) || !dst) return JDGPU_EINVAL;
+    const uint64_t nb = (n + blocksize - 1) / blocksize;
+    const uint64_t bound = bgzf_bound(n, blocksize);
+    if (!e.hin.ensure(n + 64) || !e.hout.ensure(bound + 64) || !e.hoff.ensure(nb * 8 + 64) ||
+        !e.total.ensure(64))
+        return JDGPU_EOOM;
+    hipStream_t st = e.stream;
+    order(e, st);
+    Fence fence(e, st);
+    if (n && hipMemcpyAsync(e.hin.p, src, n, hipMemcpyHostToDevice, st) != hipSuccess) return JDGPU_ENODEV;
+    const int r = bgzf_deflate_dev(e, e.hin.as<uint8_t>(), n, blocksize, level, flags, e.hout.as<uint8_t>(),
+                                   bound, e.hoff.as<uint64_t>(), e.total.as<uint64_t>(), st);
+    if (r) return r;
+    uint64_t total = 0;
+    if (hipMemcpyAsync(&total, e.total.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    if (total > bound) return JDGPU_ENODEV;         /* the bound is wrong: nothing was lost, say so */
+    if (total > cap) return JDGPU_ECAP;
+    if (hipMemcpyAsync(dst, e.hout.p, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (boffsets && nb &&
+         hipMemcpyAsync(boffsets, e.hoff.p, nb * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    return (int64) total;
+}
+
+/* candidates the index scratch holds for maxblocks members: false candidates
+ * (a member header's bytes inside a payload) are rare */
+static uint32_t bgzf_candcap(uint32_t maxblocks)
+{
+    const uint64_t c = 2ull * maxblocks + 1024;
+    return c > 0x7ffffff0ull ? 0x7ffffff0u : (uint32_t) c;
+}
+
+/* the index of d_in[0, inlen) into the caller's arrays (maxblocks entries
+ * each); res (device): nblocks, eof, status.  Caller holds the lock. */
+static int bgzf_index_dev(Engine& e, const uint8_t* d_in, uint64_t inlen, uint32_t maxblocks,
+                          uint64_t* moff, uint64_t* poff, uint32_t* psize, uint32_t* isize, uint32_t* crc,
+                          uint32_t* res, hipStream_t st)
+{
+    BScratch& b = e.bz;
+    const uint32_t cap = bgzf_candcap(maxblocks);
+    const uint64_t ng = jdk_bgzf_groups(inlen);
+    if (!b.wcnt.ensure((ng + 1) * 4 + 64) || !b.woff.ensure((ng + 1) * 8 + 64) || !b.ctotal.ensure(64) ||
+        !b.cpos.ensure((uint64_t) cap * 8 + 64) || !b.cnext.ensure((uint64_t) cap * 8 + 64) ||
+        !b.cxl.ensure((uint64_t) cap * 4 + 64) || !b.jd.ensure(((uint64_t) cap + 2) * 20 + 64))
+        return JDGPU_EOOM;
+    JdBgzfIndex X;
+    memset(&X, 0, sizeof(X));
+    X.in = d_in;
+    X.n = inlen;
+    X.maxblocks = maxblocks;
+    X.candcap = cap;
+    X.wcnt = b.wcnt.as<uint32_t>();
+    X.woff = b.woff.as<uint64_t>();
+    X.ctotal = b.ctotal.as<uint64_t>();
+    X.cpos = b.cpos.as<uint64_t>();
+    X.cnext = b.cnext.as<uint64_t>();
+    X.cxl = b.cxl.as<uint32_t>();
+    X.jd = b.jd.as<uint32_t>();
+    X.moff = moff;
+    X.poff = poff;
+    X.psize = psize;
+    X.isize = isize;
+    X.crc = crc;
+    X.nblocks = res;
+    X.eof = res + 1;
+    X.status = (int32_t*) (res + 2);
+    X.stream = st;
+    return jdk_bgzf_index_launch(&X) ? JDGPU_ENODEV : 0;
+}
+
+/* the engine's own index arrays for maxblocks members */
+static bool bgzf_index_scratch(Engine& e, uint32_t maxblocks)
+{
+    BScratch& b = e.bz;
+    const uint64_t m = maxblocks ? maxblocks : 1;
+    return b.moff.ensure(m * 8 + 64) && b.poff.ensure(m * 8 + 64) && b.psize.ensure(m * 4 + 64) &&
+           b.isize.ensure(m * 4 + 64) && b.crc.ensure(m * 4 + 64) && b.res.ensure(64);
+}
+
+JDEFLATE_API int jdgpu_bgzf_index_device(const void* d_in, uint64 inlen, uint32 maxblocks, uint64* d_moff,
+                                         uint64* d_poff, uint32* d_psize, uint32* d_isize, uint32* d_crc,
+                                         uint32* d_nblocks, uint32* d_eof, void* stream)
+{
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    if (!ready(e)) return JDGPU_ENODEV;
+    if ((inlen && !d_in) || ((uintptr_t) d_in & 15) || !d_nblocks) return JDGPU_EINVAL;
+    if (maxblocks && (!d_moff || !d_poff || !d_psize || !d_isize || !d_crc)) return JDGPU_EINVAL;
+    if (!e.bz.res.ensure(64)) return JDGPU_EOOM;
+    hipStream_t st = stream ? (hipStream_t) stream : e.stream;
+    order(e, st);
+    Fence fence(e, st);
+    uint32_t* res = e.bz.res.as<uint32_t>();
+    int r = bgzf_index_dev(e, (const uint8_t*) d_in, inlen, maxblocks, (uint64_t*) d_moff, (uint64_t*) d_poff,
+                           d_psize, d_isize, d_crc, res, st);
+    if (r) return r;
+    uint32_t h[3] = {0, 0, 0};
+    if (hipMemcpyAsync(d_nblocks, res, 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        (d_eof && hipMemcpyAsync(d_eof, res + 1, 4, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+        hipMemcpyAsync(h, res, 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    return (int32_t) h[2];
+}
+
+JDEFLATE_API int jdgpu_bgzf_index(const uint8* src, uint64 srclen, uint32 maxblocks, uint64* moff,
+                                  uint64* poff, uint32* psize, uint32* isize, uint32* crc,
+                                  uint32* nblocks, uint32* eof)
+{
+    if (srclen && !src) return JDGPU_EINVAL;
+    return jd_bgzf_walk(src, srclen, maxblocks, moff, poff, psize, isize, crc, nblocks, eof);
+}
+
+/* Decode and verify the nb members the engine's index arrays (e.bz, device)
+ * describe; hisz: their ISIZEs on the host.  d_err (device, nb) receives the
+ * per-member codes, *produced the sum of the ISIZEs.  Caller holds the lock;
+ * synchronises the stream. */
+static int bgzf_decode(Engine& e, const uint8_t* d_in, uint64_t inlen, uint32_t nb,
+                       const uint32_t* hisz, uint8_t* d_out, uint64_t outcap, int32_t* d_err,
+                       uint64_t* produced, hipStream_t st)
+{
+    BScratch& b = e.bz;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nb; i++) total += hisz[i] > 65536 ? 0 : hisz[i];
+    *produced = total;
+    if (total > outcap) return JDGPU_ECAP;
+    if (!nb) return 0;
+    if (!e.hus.ensure((uint64_t) nb * 4 + 64)) return JDGPU_EOOM;
+    const uint64_t* poff = b.poff.as<uint64_t>();
+    const uint32_t* psize = b.psize.as<uint32_t>();
+    const uint32_t* isize = b.isize.as<uint32_t>();
+    const uint32_t* crc = b.crc.as<uint32_t>();
+    uint32_t* us = e.hus.as<uint32_t>();
+
+    /* members [i0, i0 + k) decoded into dst + j * stride and verified */
+    auto run = [&](uint32_t i0, uint32_t k, uint8_t* dst, uint32_t stride) -> int {
+        JdInflateLaunch L;
+        memset(&L, 0, sizeof(L));
+        L.in = d_in;
+        L.inlen = inlen;
+        L.coff = poff + i0;
+        L.csize = psize + i0;
+        L.nblocks = k;
+        L.bs = stride;
+        L.out = dst;
+        L.usize = us + i0;
+        L.err = d_err + i0;
+        L.stream = st;
+        inflate_scratch(e, L);
+        if (jdk_inflate_launch(&L)) return JDGPU_ENODEV;
+        if (jdk_checksum_members_launch(dst, stride, k, us + i0, isize + i0, crc + i0,
+                                        e.shiftm.as<uint32_t>(), d_err + i0, JDGPU_EMEMBERSIZE,
+                                        JDGPU_EMEMBERCRC, st))
+            return JDGPU_ENODEV;
+        return 0;
+    };
+
+    /* files written here: every member but the last of one size, decoded in
+     * place (trailing empty members, the EOF marker among them, aside) */
+    uint32_t m = nb;
+    while (m && hisz[m - 1] == 0) m--;
+    const uint32_t bs = hisz[0];
+    bool same = m > 0 && bs >= 16 && bs <= 65536 && (bs & 15) == 0 && ((uintptr_t) d_out & 15) == 0 &&
+                hisz[m - 1] <= bs;
+    for (uint32_t i = 0; same && i + 1 < m; i++) same = hisz[i] == bs;
+    if (same) {
+        /* a member whose whole slot lies within the output goes there; the
+         * rest (the last one, as a rule) through a scratch slot */
+        uint64_t direct = outcap / bs;
+        if (direct > nb) direct = nb;
+        const uint32_t nd = (uint32_t) direct;
+        if (nd) {
+            const int r = run(0, nd, d_out, bs);
+            if (r) return r;
+        }
+        for (uint32_t i0 = nd; i0 < nb; i0 += JD_CHUNK_BLOCKS) {
+            const uint32_t k = nb - i0 < JD_CHUNK_BLOCKS ? nb - i0 : JD_CHUNK_BLOCKS;
+            if (!b.slots.ensure((uint64_t) k * 65536 + 256)) return JDGPU_EOOM;
+            const int r = run(i0, k, b.slots.as<uint8_t>(), 65536);
+            if (r) return r;
+            for (uint32_t j = 0; j < k; j++) {
+                const uint32_t i = i0 + j;
+                if (i < m && hisz[i] &&
+                    hipMemcpyAsync(d_out + (uint64_t) i * bs, b.slots.as<uint8_t>() + (uint64_t) j * 65536,
+                                   hisz[i], hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return JDGPU_ENODEV;
+            }
+        }
+        return hipStreamSynchronize(st) == hipSuccess ? 0 : JDGPU_ENODEV;
+    }
+
+    /* foreign files: slots of 65536, gathered by the ISIZE prefix sum (a
+     * member whose ISIZE no member can have takes no room) */
+    std::vector<uint32_t> gs(nb);
+    std::vector<uint64_t> go(nb);
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i < nb; i++) {
+        gs[i] = hisz[i] > 65536 ? 0 : hisz[i];
+        go[i] = acc;
+        acc += gs[i];
+    }
+    if (!b.gsize.ensure((uint64_t) nb * 4 + 64) || !b.goff.ensure((uint64_t) nb * 8 + 64)) return JDGPU_EOOM;
+    if (hipMemcpyAsync(b.gsize.p, gs.data(), (size_t) nb * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(b.goff.p, go.data(), (size_t) nb * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+        return JDGPU_ENODEV;
+    int r = 0;
+    for (uint32_t i0 = 0; i0 < nb && !r; i0 += JD_CHUNK_BLOCKS) {
+        const uint32_t k = nb - i0 < JD_CHUNK_BLOCKS ? nb - i0 : JD_CHUNK_BLOCKS;
+        if (!b.slots.ensure((uint64_t) k * 65536 + 256)) { r = JDGPU_EOOM; break; }
+        r = run(i0, k, b.slots.as<uint8_t>(), 65536);
+        if (!r && jdk_compact_launch(b.slots.as<uint8_t>(), 65536, b.gsize.as<uint32_t>() + i0,
+                                     b.goff.as<uint64_t>() + i0, k, d_out, outcap, st))
+            r = JDGPU_ENODEV;
+    }
+    /* the uploads read gs / go */
+    if (hipStreamSynchronize(st) != hipSuccess && !r) r = JDGPU_ENODEV;
+    return r;
+}
+
+/* 0, or JDGPU_EDATA when a member failed (herr: nb host entries) */
+static int bgzf_any_error(const int32_t* herr, uint32_t nb)
+{
+    for (uint32_t i = 0; i < nb; i++)
+        if (herr[i]) return JDGPU_EDATA;
+    return 0;
+}
+
+JDEFLATE_API int jdgpu_bgzf_inflate_device(const void* d_in, uint64 inlen, void* d_out, uint64 outcap,
+                                           uint64* d_total, int32* d_errors, uint32 maxblocks,
+                                           void* stream)
+{
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    if (!ready(e)) return JDGPU_ENODEV;
+    if ((inlen && !d_in) || ((uintptr_t) d_in & 15) || (!d_out && outcap) || !d_total ||
+        (maxblocks && !d_errors))
+        return JDGPU_EINVAL;
+    if (!bgzf_index_scratch(e, maxblocks)) return JDGPU_EOOM;
+    hipStream_t st = stream ? (hipStream_t) stream : e.stream;
+    order(e, st);
+    Fence fence(e, st);
+    BScratch& b = e.bz;
+    uint32_t* res = b.res.as<uint32_t>();
+    int r = bgzf_index_dev(e, (const uint8_t*) d_in, inlen, maxblocks, b.moff.as<uint64_t>(),
+                           b.poff.as<uint64_t>(), b.psize.as<uint32_t>(), b.isize.as<uint32_t>(),
+                           b.crc.as<uint32_t>(), res, st);
+    if (r) return r;
+    uint32_t h[3] = {0, 0, 0};
+    if (hipMemsetAsync(d_total, 0, 8, st) != hipSuccess ||
+        hipMemcpyAsync(h, res, 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    if ((int32_t) h[2]) return (int32_t) h[2];
+    const uint32_t nb = h[0];
+    std::vector<uint32_t> hisz(nb);
+    std::vector<int32_t> herr(nb);
+    if (nb && (hipMemcpyAsync(hisz.data(), b.isize.p, (size_t) nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+               hipStreamSynchronize(st) != hipSuccess))
+        return JDGPU_ENODEV;
+    uint64_t produced = 0;
+    r = bgzf_decode(e, (const uint8_t*) d_in, inlen, nb, hisz.data(), (uint8_t*) d_out, outcap,
+                    (int32_t*) d_errors, &produced, st);
+    if (r) return r;
+    if (hipMemcpyAsync(d_total, &produced, 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (nb && hipMemcpyAsync(herr.data(), d_errors, (size_t) nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    return bgzf_any_error(herr.data(), nb);
+}
+
+JDEFLATE_API int jdgpu_bgzf_inflate(const uint8* src, uint64 srclen, uint8* dst, uint64 cap,
+                                    uint64* produced, uint32* nblocks, uint32* eof, int32* errors)
+{
+    if ((srclen && !src) || (cap && !dst)) return JDGPU_EINVAL;
+    /* the walk on the host, the index uploaded */
+    uint32_t nb = 0, iseof = 0;
+    int r = jd_bgzf_walk(src, srclen, 0xffffffffu, nullptr, nullptr, nullptr, nullptr, nullptr, &nb, &iseof);
+    if (nblocks) *nblocks = nb;
+    if (eof) *eof = iseof;
+    if (produced) *produced = 0;
+    if (r) return r;
+    std::vector<uint64_t> poff(nb);
+    std::vector<uint32_t> psize(nb), isize(nb), crc(nb);
+    std::vector<int32_t> herr(nb);
+    (void) jd_bgzf_walk(src, srclen, nb, nullptr, poff.data(), psize.data(), isize.data(), crc.data(),
+                        nullptr, nullptr);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nb; i++) total += isize[i] > 65536 ? 0 : isize[i];
+    if (total > cap) return JDGPU_ECAP;
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    if (!ready(e)) return JDGPU_ENODEV;
+    if (!bgzf_index_scratch(e, nb) || !e.hin.ensure(srclen + 64) || !e.hout.ensure(total + 64) ||
+        !e.herr.ensure((uint64_t) nb * 4 + 64))
+        return JDGPU_EOOM;
+    hipStream_t st = e.stream;
+    order(e, st);
+    Fence fence(e, st);
+    BScratch& b = e.bz;
+    if (nb && (hipMemcpyAsync(e.hin.p, src, srclen, hipMemcpyHostToDevice, st) != hipSuccess ||
+               hipMemcpyAsync(b.poff.p, poff.data(), (size_t) nb * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+               hipMemcpyAsync(b.psize.p, psize.data(), (size_t) nb * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+               hipMemcpyAsync(b.isize.p, isize.data(), (size_t) nb * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+               hipMemcpyAsync(b.crc.p, crc.data(), (size_t) nb * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+               hipStreamSynchronize(st) != hipSuccess))
+        return JDGPU_ENODEV;
+    uint64_t prod = 0;
+    r = bgzf_decode(e, e.hin.as<uint8_t>(), srclen, nb, isize.data(), e.hout.as<uint8_t>(), total,
+                    e.herr.as<int32_t>(), &prod, st);
+    if (r) return r;
+    if ((total && hipMemcpyAsync(dst, e.hout.p, total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (nb && hipMemcpyAsync(herr.data(), e.herr.p, (size_t) nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JDGPU_ENODEV;
+    if (produced) *produced = total;
+    if (errors)
+        for (uint32_t i = 0; i < nb; i++) errors[i] = herr[i];
+    return bgzf_any_error(herr.data(), nb);
 }
 
 /* ---- one RFC 1951 stream: the resumable decoder ------------------------

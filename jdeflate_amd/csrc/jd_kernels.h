@@ -18,7 +18,8 @@ typedef struct {
     uint32_t nblocks;       /* ceil(n / bs), >= 1                        */
     int level;              /* 0..9                                      */
     uint32_t flags;         /* DEFLT_FIXEDCODES                          */
-    uint32_t lastfinal;     /* 1: last block ends with BFINAL=1          */
+    uint32_t lastfinal;     /* BFINAL=1 on: 0 no block, 1 the last block,
+                               2 every block (BGZF members)              */
     uint16_t* chains;       /* device: 5 * nslots + 128 uint16: links,
                                then the slices (jdk_deflate_launch)      */
     uint32_t* tokens;       /* device: nslots uint32                     */
@@ -28,7 +29,8 @@ typedef struct {
     uint8_t* stage;         /* device: nblocks * slotcap                 */
     uint32_t slotcap;
     uint32_t* csize;        /* device: nblocks                           */
-    uint64_t* coff;         /* device: nblocks                           */
+    uint64_t* coff;         /* device: nblocks (NULL: no offset scan and
+                               no concatenation; total is not written)  */
     uint64_t* total;        /* device: 1                                 */
     const uint64_t* base;   /* device: offset of this chunk (NULL = 0)   */
     uint8_t* out;           /* device: compacted output (may be NULL)    */

@@ -13,6 +13,7 @@ enum {
     JDK_SCAN, JDK_COMPACT, JDK_INFLATE, JDK_INFLATE_P1, JDK_INFLATE_P2,
     JDK_PSPEC, JDK_PSYNC, JDK_PJOIN, JDK_CHECKSUM, JDK_INFLATE_MP,
     JDK_FSP_FIND, JDK_FSP_DECODE, JDK_FSP_WINDOW, JDK_FSP_RESOLVE, JDK_INFLATE_RPAR, JDK_PORDER,
+    JDK_BGZF_FRAME, JDK_BGZF_INDEX, JDK_BGZF_VERIFY,
     JDK_COUNT
 };
 

@@ -34,7 +34,10 @@ INFLT_OK, INFLT_SRCEXHSTD, INFLT_TGTEXHSTD, INFLT_ERROR = 0, 1, 2, 3
  INFLT_EBADBLOCK, INFLT_EINPUTEND, INFLT_EOOM, INFLT_EINCORRECTUSE) = range(1, 9)
 
 JDGPU_EINVAL, JDGPU_ENODEV, JDGPU_EOOM, JDGPU_ECAP, JDGPU_EDATA = -1, -2, -3, -4, -5
+JDGPU_EBLOCKOVERFLOW, JDGPU_EMEMBERSIZE, JDGPU_EMEMBERCRC = 9, 10, 11
 BLOCKSIZE = 65536
+BGZF_BLOCKSIZE = 65280           # htslib's input bytes per member
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 # every symbol the C ABI exports (include/jdeflate/*.h)
 EXPORTS = (
@@ -52,6 +55,9 @@ EXPORTS = (
     "jdgpu_istream_stats", "jdgpu_istream_fsp", "jdgpu_istream_rpar", "jdgpu_istream_queue",
     "jdgpu_istream_destroy", "jdgpu_deflate_multi", "jdgpu_deflate_multi_device",
     "jdgpu_inflate_multi",
+    "jdgpu_bgzf_bound", "jdgpu_bgzf_deflate_device", "jdgpu_bgzf_deflate",
+    "jdgpu_bgzf_index_device", "jdgpu_bgzf_index", "jdgpu_bgzf_inflate_device",
+    "jdgpu_bgzf_inflate",
     "zstrm_create", "zstrm_destroy", "zstrm_setsource", "zstrm_setsourcefn",
     "zstrm_settargetfn", "zstrm_setdctnr", "zstrm_inflate", "zstrm_deflate", "zstrm_flush",
     "zstrm_reset", "zstrm_crc32combine", "zstrm_crc32update", "zstrm_adler32update",
@@ -68,7 +74,7 @@ KERNELS = ("k_chains<4>", "k_chains<3>", "k_match", "k_parse", "k_emit", "k_stor
            "k_scan", "k_compact", "k_inflate", "k_inflate_par", "k_inflate_resolve",
            "k_pspec", "k_psync", "k_pjoin", "k_checksum", "k_inflate_mp",
            "k_fsp_find", "k_fsp_decode", "k_fsp_window", "k_fsp_resolve", "k_inflate_rpar",
-           "k_porder")
+           "k_porder", "k_bgzf_frame", "k_bgzf_scan", "k_checksum_members")
 
 
 class _ZPublic(ctypes.Structure):
@@ -276,6 +282,34 @@ def load_library(path: str = LIBPATH) -> ctypes.CDLL:
     L.jdgpu_istream_queue.argtypes = [ctypes.c_void_p]
     L.jdgpu_istream_destroy.restype = None
     L.jdgpu_istream_destroy.argtypes = [ctypes.c_void_p]
+    if hasattr(L, "jdgpu_bgzf_bound"):             # (dev A/B builds may predate it)
+        L.jdgpu_bgzf_bound.restype = ctypes.c_uint64
+        L.jdgpu_bgzf_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        L.jdgpu_bgzf_deflate_device.restype = ctypes.c_int
+        L.jdgpu_bgzf_deflate_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.jdgpu_bgzf_deflate.restype = ctypes.c_int64
+        L.jdgpu_bgzf_deflate.argtypes = [
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint64, c_u64p]
+        L.jdgpu_bgzf_index_device.restype = ctypes.c_int
+        L.jdgpu_bgzf_index_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p]
+        L.jdgpu_bgzf_index.restype = ctypes.c_int
+        L.jdgpu_bgzf_index.argtypes = [
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, c_u64p, c_u64p, c_u32p, c_u32p, c_u32p,
+            c_u32p, c_u32p]
+        L.jdgpu_bgzf_inflate_device.restype = ctypes.c_int
+        L.jdgpu_bgzf_inflate_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        L.jdgpu_bgzf_inflate.restype = ctypes.c_int
+        L.jdgpu_bgzf_inflate.argtypes = [
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, c_u64p, c_u32p, c_u32p,
+            c_i32p]
     ZP = ctypes.POINTER(_ZPublic)
     L.zstrm_create.restype = ZP
     L.zstrm_create.argtypes = [ctypes.c_size_t, ctypes.c_ssize_t, ctypes.c_void_p]
@@ -458,6 +492,119 @@ def inflate_device(d_in: int, inlen: int, d_coffs: int, d_csizes: int, nb: int,
                                             d_out, d_usizes, d_errors, stream or None)
     if r:
         raise RuntimeError(f"jdgpu_inflate_device failed: {r}")
+
+
+class BgzfError(RuntimeError):
+    """A BGZF call failed: .code is the JDGPU_E* value; .members, when the
+    members were counted, their number (the good ones of a broken chain);
+    .errors the per-member codes of an inflate."""
+
+    def __init__(self, what, code, members=None, errors=None):
+        super().__init__(f"{what} failed: {code}")
+        self.code, self.members, self.errors = code, members, errors
+
+
+def bgzf_bound(n: int, blocksize: int = BGZF_BLOCKSIZE) -> int:
+    return int(load_library().jdgpu_bgzf_bound(n, blocksize))
+
+
+def bgzf_compress(data: bytes, level: int = 6, blocksize: int = BGZF_BLOCKSIZE, flags: int = 0,
+                  offsets: list | None = None, cap: int | None = None) -> bytes:
+    """BGZF on the GPU: one gzip member per `blocksize` bytes, then the EOF
+    marker.  offsets (a list, optional) receives the member offsets."""
+    L = _need()
+    n = len(data)
+    if cap is None:
+        cap = bgzf_bound(n, blocksize)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    nb = -(-n // blocksize) if blocksize else 0
+    bo = (ctypes.c_uint64 * max(nb, 1))()
+    r = L.jdgpu_bgzf_deflate(bytes(data), n, blocksize, level, flags, out, cap, bo)
+    if r < 0:
+        raise BgzfError("jdgpu_bgzf_deflate", r)
+    if offsets is not None:
+        offsets[:] = list(bo)[:nb]
+    return out.raw[:r]
+
+
+def bgzf_index(data: bytes, maxblocks: int | None = None, full: bool = False):
+    """The members of a BGZF buffer, walked on the host (no GPU): a list of
+    (offset, payload_size, isize, crc); full=True: (list of (offset,
+    payload_offset, payload_size, isize, crc), eof).  BgzfError (.code
+    JDGPU_EDATA, .members good ones) on a broken chain."""
+    L = load_library()
+    src = bytes(data)
+    if maxblocks is None:
+        maxblocks = len(src) // 26 + 1
+    m = max(maxblocks, 1)
+    mo, po = (ctypes.c_uint64 * m)(), (ctypes.c_uint64 * m)()
+    ps, isz, crc = (ctypes.c_uint32 * m)(), (ctypes.c_uint32 * m)(), (ctypes.c_uint32 * m)()
+    nb, eof = ctypes.c_uint32(), ctypes.c_uint32()
+    r = L.jdgpu_bgzf_index(src, len(src), maxblocks, mo, po, ps, isz, crc, ctypes.byref(nb),
+                           ctypes.byref(eof))
+    rows = [(mo[i], po[i], ps[i], isz[i], crc[i]) for i in range(nb.value)]
+    if r:
+        raise BgzfError("jdgpu_bgzf_index", r, members=rows)
+    if full:
+        return rows, bool(eof.value)
+    return [(a, c, d, e) for a, _, c, d, e in rows]
+
+
+def bgzf_decompress(data: bytes, errors: list | None = None) -> bytes:
+    """Inflate a BGZF buffer on the GPU (members walked on the host, decoded
+    in parallel, each verified against its ISIZE and CRC-32).  BgzfError
+    (.code JDGPU_EDATA, .errors per member, .data the bytes) when a member
+    fails; errors (a list, optional) receives the per-member codes."""
+    L = _need()
+    src = bytes(data)
+    try:
+        rows = bgzf_index(src)
+    except BgzfError as ex:
+        raise BgzfError("jdgpu_bgzf_inflate", ex.code, members=ex.members) from None
+    cap = sum(r[2] for r in rows if r[2] <= 65536)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    er = (ctypes.c_int32 * max(len(rows), 1))()
+    prod, nb, eof = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+    r = L.jdgpu_bgzf_inflate(src, len(src), out, cap, ctypes.byref(prod), ctypes.byref(nb),
+                             ctypes.byref(eof), er)
+    codes = list(er)[:len(rows)]
+    if errors is not None:
+        errors[:] = codes
+    if r:
+        ex = BgzfError("jdgpu_bgzf_inflate", r, members=rows, errors=codes)
+        ex.data = out.raw[:cap] if r == JDGPU_EDATA else b""
+        raise ex
+    return out.raw[:prod.value]
+
+
+def bgzf_deflate_device(d_in: int, n: int, d_out: int, outcap: int, d_boffsets: int, d_total: int,
+                        level: int = 6, blocksize: int = BGZF_BLOCKSIZE, flags: int = 0,
+                        stream: int = 0) -> None:
+    """Asynchronous device-resident BGZF deflate (pointers are device addresses)."""
+    r = load_library().jdgpu_bgzf_deflate_device(d_in, n, blocksize, level, flags, d_out, outcap,
+                                                 d_boffsets or None, d_total, stream or None)
+    if r:
+        raise BgzfError("jdgpu_bgzf_deflate_device", r)
+
+
+def bgzf_index_device(d_in: int, inlen: int, maxblocks: int, d_moff: int, d_poff: int, d_psize: int,
+                      d_isize: int, d_crc: int, d_nblocks: int, d_eof: int, stream: int = 0) -> int:
+    """Device index of a BGZF buffer; returns 0, JDGPU_EDATA or JDGPU_ECAP."""
+    r = load_library().jdgpu_bgzf_index_device(d_in, inlen, maxblocks, d_moff, d_poff, d_psize,
+                                               d_isize, d_crc, d_nblocks, d_eof, stream or None)
+    if r not in (0, JDGPU_EDATA, JDGPU_ECAP):
+        raise BgzfError("jdgpu_bgzf_index_device", r)
+    return r
+
+
+def bgzf_inflate_device(d_in: int, inlen: int, d_out: int, outcap: int, d_total: int, d_errors: int,
+                        maxblocks: int, stream: int = 0) -> int:
+    """Device-resident BGZF inflate; returns 0 or JDGPU_EDATA (see d_errors)."""
+    r = load_library().jdgpu_bgzf_inflate_device(d_in, inlen, d_out, outcap, d_total, d_errors,
+                                                 maxblocks, stream or None)
+    if r not in (0, JDGPU_EDATA):
+        raise BgzfError("jdgpu_bgzf_inflate_device", r)
+    return r
 
 
 class Deflator:
